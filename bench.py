@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — PCG subproblems/s + achieved HBM GB/s of the dominant kernel, BASELINE config 3 per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds what is measured beside the
+headline, each after the timed region: the dense event sample of the fused kernel, back-to-back J*v / J'*u / J'(J*p) and
+read-probe launches, the ill-conditioned variant, the CPU baseline and, with N > 1, the exchange timings.  `--dump-outputs DIR`
+writes what the last timed step returned to its caller (w, status, iters, n_hmul) as DIR/<name>.npy in float64.
 
 A step = one complete projected_cg subproblem (bh_pcg_dev: initial projection -> CG loop -> status) on the synthetic
 dense NLS instance of SURVEY.md §8(d): box bounds with p = 512 active, mu = 10, kappa2 = 0.1; all vectors are resident in
@@ -266,7 +271,14 @@ def main():
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--no-ic-extra", action="store_true",
                     help="skip the ill-conditioned extra run (its over-launched no-op kernels would pull down rocprofv3's per-kernel average)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline (dense sample, kernel timings, ill-conditioned variant, CPU "
+                         "baseline, exchange timings); --no-extras / --no-ic-extra / --no-cpu-baseline trim them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write w, status, iters and n_hmul of the last step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # typed as `python bench.py --gpus N`: be the launcher (before anything here imports torch or touches HIP)
@@ -410,7 +422,7 @@ def main():
     # hipEvents around H*p launches INSIDE the timed region: an event pair costs ~10 us of stream time, so bracketing every launch
     # slows the loop it measures (measured at K = 20: 690 instead of 630 us per subproblem, -9 %).  Long runs sample every 8th
     # launch, short ones every 4th (10 samples at K = 20, < 1 % cost); a DENSE pass outside the timed region (every launch of
-    # 16 subproblems) is reported next to it as roofline.dense_sample.
+    # 16 subproblems) is reported next to it as roofline.dense_sample (--full only).
     st_probe = run_steps(bh, H, cons, dv, kappa2, 1)
     timed_stride = 4 if args.steps * st_probe[2] <= 64 else 8
     timed_stride = int(os.environ.get("BH_BENCH_EV_STRIDE", timed_stride))
@@ -468,6 +480,7 @@ def main():
             if valid and el_p < elapsed:
                 elapsed, st, (status, iters, n_hmul) = el_p, st_p, out_p
                 replicas_identical, headline_transport, other_run = ident_p, "peer_buffers", rccl_run
+                w_headline = w_peer
             else:
                 other_run = peer_run
         try:
@@ -475,21 +488,29 @@ def main():
         except bh.BenlsipHipError:
             pass
 
+    if args.dump_outputs is not None and rank == 0:
+        # what the last timed step handed its caller: w (replicated at N > 1: the headline run's), status, iters, n_hmul
+        w_out = w_headline if w_headline is not None else dv["w"].download()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("w", w_out), ("status", [int(status)]), ("iters", [iters]), ("n_hmul", [n_hmul])):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(a, dtype=np.float64))
+
     # dense sample, outside the timed region: every H*p launch of 16 subproblems bracketed by events (all ranks do the same calls)
     dense = None
-    try:
-        bh.set_option("profile_stride", 1)
-        H.reset_stats()
-        run_steps(bh, H, cons, dv, kappa2, 16)
-        barrier_noexcept()
-        sd = H.stats()
-        if sd["hmul_timed"] > 0:
-            d_ms = sd["hmul_ms"] / sd["hmul_timed"]
-            dense = {"launches_timed": sd["hmul_timed"], "avg_launch_ms": d_ms, "achieved": sd["bytes_per_hmul"] / (d_ms * 1e-3) / 1e9,
-                     "note": "every H*p launch of 16 subproblems after the timed region, hipEvents on the launch stream"}
-    except bh.BenlsipHipError:
-        dense = None
-    bh.set_option("profile_stride", timed_stride)
+    if args.full:
+        try:
+            bh.set_option("profile_stride", 1)
+            H.reset_stats()
+            run_steps(bh, H, cons, dv, kappa2, 16)
+            barrier_noexcept()
+            sd = H.stats()
+            if sd["hmul_timed"] > 0:
+                d_ms = sd["hmul_ms"] / sd["hmul_timed"]
+                dense = {"launches_timed": sd["hmul_timed"], "avg_launch_ms": d_ms, "achieved": sd["bytes_per_hmul"] / (d_ms * 1e-3) / 1e9,
+                         "note": "every H*p launch of 16 subproblems after the timed region, hipEvents on the launch stream"}
+        except bh.BenlsipHipError:
+            dense = None
+        bh.set_option("profile_stride", timed_stride)
 
     traffic, traffic_src = pmc_traffic(args.config) if world == 1 else (None, None)
     ms_per_step = 1e3 * elapsed / args.steps
@@ -559,11 +580,11 @@ def main():
                 return None
             return float(g.max())
 
-        if comm_mode in ("rccl", "both"):
+        if args.full and comm_mode in ("rccl", "both"):
             bh.set_option("comm_path", 0)
             comm["rccl_allreduce_us"] = timed_exchange(7)
             comm["rccl_reduce_plus_allreduce_us"] = timed_exchange(8)
-        if comm_mode in ("ipc", "both"):
+        if args.full and comm_mode in ("ipc", "both"):
             # every decision below is taken from gathered values, so all ranks walk through the same collectives even when the
             # peer exchange fails on some of them (it then times out, raises there and is reported as comm["error"])
             try:
@@ -585,7 +606,7 @@ def main():
         line["comm"] = comm
         line["allreduce_us"] = comm["allreduce_us"]
     # (a peer-buffer-only run whose exchange failed has no working all-reduce left: the line is printed without the extras)
-    if not args.no_extras and not (world > 1 and comm_mode == "ipc" and line["comm"].get("error")):
+    if args.full and not args.no_extras and not (world > 1 and comm_mode == "ipc" and line["comm"].get("error")):
         d_loc = host["hi"] - host["lo"]
         mv_bytes = 8.0 * d_loc * N_COLS + 8.0 * N_COLS + 8.0 * d_loc
         ms_f, ms_jv, ms_jtv = (H.time_kernel(k, 20) for k in (0, 1, 2))
@@ -606,7 +627,7 @@ def main():
             "note": "read_probe_kernel: 16-byte non-temporal loads + adds only, same J image; what a single-read kernel can reach here",
         }
         line["post_stream_us"] = 1e3 * H.time_kernel(8, 200) if world == 1 else None    # slab reduction after the streaming kernel
-    if world == 1 and not args.no_extras and not args.no_ic_extra and args.variant == "wc":
+    if args.full and world == 1 and not args.no_extras and not args.no_ic_extra and args.variant == "wc":
         # steady-state CG iteration cost on the ill-conditioned variant (23 iterations per subproblem): outside the timed region
         # (the first handle stays allocated: freeing 2 GiB here makes the driver scrub it in the background, which took
         # ~5 % of the HBM bandwidth from the next ~60 ms of kernels — tools/ic_transient.py)
@@ -621,7 +642,7 @@ def main():
                               "hmul_per_subproblem": nh2, "ms_per_subproblem": 1e3 * el2, "ms_per_cg_iteration": 1e3 * el2 / max(nh2, 1),
                               "subproblems_per_s": 1.0 / el2,
                               "cg_iteration_gbs": st["bytes_per_hmul"] / (el2 / max(nh2, 1)) / 1e9}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(kind, kappa2, n_hmul, config=args.config)
     elif rank == 0:
         line["cpu_baseline"] = None

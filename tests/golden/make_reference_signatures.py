@@ -1,12 +1,13 @@
 """Writes tests/golden/reference_signatures.json: for every `function name(...)` in the reference's live source files, its name and
 its first line, the number, names and type annotations of its POSITIONAL parameters (keywords after `;` listed separately); the field names of its structs, the members of `CG_status` and the length of each file.  Data about the reference's interface — what
-the Julia shim's more specific methods must line up with — not its source.  Run here (needs /root/reference); the fixture is committed.
-    python tests/golden/make_reference_signatures.py"""
+the Julia shim's more specific methods must line up with — not its source.  Needs a checkout of the reference, named by
+BENLSIP_REF_SRC (its src/ directory); the fixture is committed.
+    BENLSIP_REF_SRC=<reference>/src python tests/golden/make_reference_signatures.py"""
 import json
 import os
 import re
 
-REF = "/root/reference/src"
+REF = os.environ.get("BENLSIP_REF_SRC", "")          # the reference's src/ directory; empty: not available
 FILES = ["basic_tralcnlss.jl", "polyhedral_constraints.jl"]
 
 
@@ -64,6 +65,8 @@ def build():
 
 
 def main():
+    if not os.path.isdir(REF):
+        raise SystemExit("set BENLSIP_REF_SRC to the reference's src/ directory")
     out = build()
     dst = os.path.join(os.path.dirname(os.path.abspath(__file__)), "reference_signatures.json")
     json.dump(out, open(dst, "w"), indent=1, sort_keys=True)

@@ -1,6 +1,6 @@
 """Manual check (not collected): n above the register-resident limit (column panels) with linear equalities, every CG iteration shape, against the oracle."""
 import os, sys
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")): sys.path.insert(0, p)
 import numpy as np
 import benlsip_jl_amd as bh, benlsip_ref as R

@@ -2,7 +2,7 @@
 projected_cg fuzz cases per seed against the C oracle, 25 cauchy_step + minor_iterate cases per caller seed against the
 NumPy oracle, then 6000 repeated config-3 subproblems that must return bit-identical results."""
 import os, sys, time
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import benlsip_jl_amd as bh

@@ -6,7 +6,8 @@
 #      steps run on each, the valid and faster run becomes the headline, and the comm section times both all-reduces.
 R=$GRAFT_REPO_ROOT
 cd $R
-mkdir -p gpurun_out
+LOG=${BH_LOG_DIR:-logs}
+mkdir -p $LOG
 export BH_BENCH_REHEARSAL=1
 rc=0
 #   3. the same with rank 1 staying away from the peer exchange (BH_BENCH_FAULT_RANK): rank 0 runs into the exchange's timeout;
@@ -25,15 +26,15 @@ for cfg in "2 weak ipc" "3 strong ipc" "2 weak both" "2 weak both fault" "2 weak
     fi
     if [ "$3" = "ipc" ]; then
         # as typed, without a launcher: bench.py starts its ranks itself (child processes; the launcher never touches HIP)
-        timeout -k 10 400 python bench.py --gpus $1 --steps 20 --warmup 2 --scaling $2 > gpurun_out/bench_rehearsal_$1_$2_$3$4.log 2>&1 || rc=$?
+        timeout -k 10 400 python bench.py --gpus $1 --steps 20 --warmup 2 --scaling $2 --full > $LOG/bench_rehearsal_$1_$2_$3$4.log 2>&1 || rc=$?
     else
         timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $1 --master-addr 127.0.0.1 --master-port 2953$1 \
-            bench.py --gpus $1 --steps 20 --warmup 2 --scaling $2 > gpurun_out/bench_rehearsal_$1_$2_$3$4.log 2>&1 || rc=$?
+            bench.py --gpus $1 --steps 20 --warmup 2 --scaling $2 --full > $LOG/bench_rehearsal_$1_$2_$3$4.log 2>&1 || rc=$?
     fi
     rm -f /dev/shm/bh_rehearsal_$$
-    tail -1 gpurun_out/bench_rehearsal_$1_$2_$3$4.log | cut -c1-1200
-    if [ "$3" = "auto" ]; then grep -q 'fell back to BH_COMM=ipc' gpurun_out/bench_rehearsal_$1_$2_$3$4.log || { echo "auto: no fall-back note"; rc=1; }; fi
-    grep -o '"comm": {[^}]*}[^}]*}' gpurun_out/bench_rehearsal_$1_$2_$3$4.log | cut -c1-900
-    [ $rc -eq 0 ] || { tail -30 gpurun_out/bench_rehearsal_$1_$2_$3$4.log; exit $rc; }
+    tail -1 $LOG/bench_rehearsal_$1_$2_$3$4.log | cut -c1-1200
+    if [ "$3" = "auto" ]; then grep -q 'fell back to BH_COMM=ipc' $LOG/bench_rehearsal_$1_$2_$3$4.log || { echo "auto: no fall-back note"; rc=1; }; fi
+    grep -o '"comm": {[^}]*}[^}]*}' $LOG/bench_rehearsal_$1_$2_$3$4.log | cut -c1-900
+    [ $rc -eq 0 ] || { tail -30 $LOG/bench_rehearsal_$1_$2_$3$4.log; exit $rc; }
 done
 exit $rc
