@@ -134,6 +134,7 @@ struct Ctx {
     int64_t opt_proj_form = 1;       // 1: reduced mA x mA form (fast), 0: the reference's augmented mpp x mpp form
     int64_t opt_upload_chunk_mb = 64; // bh_hess_create_async: MiB of J per pipelined column chunk
     int64_t opt_ev_stride = 8;       // BH_FLAG_PROFILE: hipEvents around every opt_ev_stride-th H*p launch of a handle
+    int64_t opt_gram_nt = 1;         // Gram form: G·v with non-temporal loads (1, measured faster at every size: profiles/r04_gn_gram_timing.txt) or plain (0)
     int64_t opt_pingpong = 0;        // alternate the sweep direction of J between consecutive H*p products (A/B: +1 % without nt loads, -0.2 % with)
     // RCCL
     void* rccl_lib = nullptr;
@@ -413,6 +414,15 @@ struct bh_hess {
     uint64_t hmul_seq = 0;         // H*p launches of bh_pcg calls on this handle (profile sampling)
     bool counted = false;          // included in g_ctx.live_hess (false while a create is failing)
     bool pending_finish = false;   // bh_hess_create_async on a rank without rows: the d_total collective runs at wait / first use, as on its peers
+    // explicit Gram form (bh_hess_set_form): G = J'J + mu C'C as an ld x ld row-major image, built on first use after it went stale
+    int form = BH_HESS_IMPLICIT;
+    double* G = nullptr;           // ld x ld (allocated while form == BH_HESS_GRAM)
+    double* gpart = nullptr;       // gram_slabs x ld x ld: per-slab partial sums of a build split over row slabs (small n only)
+    int gram_slabs = 1;
+    int64_t gram_slab_rows = 0;
+    bool G_valid = false;          // G belongs to the current J and to G_mu
+    double G_mu = 0.0;             // the mu G was built with
+    int64_t gram_builds = 0;
 };
 
 struct bh_proj {
@@ -623,10 +633,104 @@ int32_t profile_begin(bh_hess* H, int ev_index, int* slot) {
     return BH_OK;
 }
 
+// Algorithmic bytes of one H*p launch in the handle's current form (bh_stats_t.bytes_per_hmul).
+double hmul_bytes(const bh_hess* H) {
+    if (H->form == BH_HESS_GRAM) return 8.0 * (double)H->n * (double)H->ld + 16.0 * (double)H->n;
+    return (multi_panel(H) ? 16.0 : 8.0) * (double)(H->d + H->q_eff) * (double)H->n + 16.0 * (double)H->n;
+}
+
+// ---- explicit Gram form --------------------------------------------------------------------------------------------------
+// Row slabs of a build: one when the 64 x 64 lower blocks of G already outnumber the CUs, else enough slabs for ~2 workgroups
+// per CU, each of at least 256 rows.
+void gram_geometry(const bh_hess* H, int* nslabs, int64_t* slab_rows) {
+    const int64_t nrows = H->d + H->q_eff;
+    const int64_t nb = (H->ld + GNG_BS - 1) / GNG_BS, nlb = nb * (nb + 1) / 2;
+    int64_t s = 1;
+    if (nlb < g_ctx.n_cu) s = std::max<int64_t>(1, std::min<int64_t>((2 * g_ctx.n_cu + nlb - 1) / nlb, (nrows + 255) / 256));
+    int64_t rows = round_up(std::max<int64_t>((nrows + s - 1) / s, 1), 16);
+    s = std::max<int64_t>(1, (nrows + rows - 1) / rows);
+    *nslabs = (int)s;
+    *slab_rows = rows;
+}
+
+// G = J'J + mu C'C on the library stream (after the image is complete).  No host synchronisation.
+int32_t launch_gram_build(bh_hess* H) {
+    BH_TRY(hess_ready(H));
+    const int64_t nb = (H->ld + GNG_BS - 1) / GNG_BS;
+    const unsigned nlb = (unsigned)(nb * (nb + 1) / 2);
+    const int64_t nrows = H->d + H->q_eff;
+    const bool split = H->gram_slabs > 1;
+    hipLaunchKernelGGL(gn_gram_mfma_kernel, dim3(nlb, (unsigned)H->gram_slabs), dim3(GNG_T), 0, g_ctx.stream, (const double*)H->Jd, H->ld,
+                       nrows, H->d, H->mu, H->gram_slab_rows, H->G, split ? H->gpart : nullptr);
+    if (split) {
+        const int64_t blocks = std::min<int64_t>((H->ld * H->ld + 255) / 256, (int64_t)g_ctx.n_cu * 8);
+        hipLaunchKernelGGL(gn_gram_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, g_ctx.stream, (const double*)H->gpart, H->gram_slabs,
+                           H->ld, H->G);
+    }
+    BH_HIP(hipGetLastError());
+    H->G_valid = true;
+    H->G_mu = H->mu;
+    H->gram_builds += 1;
+    return BH_OK;
+}
+
+int32_t ensure_gram(bh_hess* H) {
+    if (H->G_valid) return BH_OK;
+    return launch_gram_build(H);
+}
+
+// G·v: row_stream_kernel in J·v mode over the G image (ld rows, every weight 1; the padding rows of G are zero, so z_out's
+// padding comes out zero).  NT = 1: non-temporal loads — faster than plain loads although G is re-read by every product
+// (config 3: 21.9 against 22.4 us; n = 8192: 78.3 against 86.5 us; profiles/r04_gn_gram_timing.txt).
+template <int NT>
+void launch_gram_gv_nt(int64_t nchunks, const RowStreamArgs& a, hipStream_t s) {
+    int cfg;
+    if (nchunks <= 64) cfg = 0;
+    else if (nchunks <= 256) cfg = 1;
+    else if (nchunks <= 512) cfg = 2;
+    else if (nchunks <= 1024) cfg = 3;
+    else if (nchunks <= 2048) cfg = 4;
+    else if (nchunks <= 4096) cfg = 5;
+    else cfg = 14;
+    const int grid = grid_for(cfg, a.nrows);
+    switch (cfg) {
+        case 0: hipLaunchKernelGGL((row_stream_kernel<64, 1, 8, MODE_JV, NT>), dim3(grid), dim3(64), 0, s, a); break;
+        case 1: hipLaunchKernelGGL((row_stream_kernel<256, 1, 8, MODE_JV, NT>), dim3(grid), dim3(256), 0, s, a); break;
+        case 2: hipLaunchKernelGGL((row_stream_kernel<256, 2, 8, MODE_JV, NT>), dim3(grid), dim3(256), 0, s, a); break;
+        case 3: hipLaunchKernelGGL((row_stream_kernel<256, 4, 4, MODE_JV, NT>), dim3(grid), dim3(256), 0, s, a); break;
+        case 4: hipLaunchKernelGGL((row_stream_kernel<256, 8, 4, MODE_JV, NT>), dim3(grid), dim3(256), 0, s, a); break;
+        case 5: hipLaunchKernelGGL((row_stream_kernel<512, 8, 2, MODE_JV, NT>), dim3(grid), dim3(512), 0, s, a); break;
+        default: hipLaunchKernelGGL((row_stream_kernel<512, 16, 1, MODE_JV, NT>), dim3(grid), dim3(512), 0, s, a); break;
+    }
+}
+
+void launch_gram_gv(bh_hess* H, const double* v_pad, double* z_out, const CgState* state, bool negate, const int* negmask) {
+    RowStreamArgs a{};
+    a.J = H->G; a.ld = H->ld; a.nrows = H->ld; a.d_rows = H->ld; a.nchunks = H->nchunks; a.mu = 1.0; a.state = state;
+    a.v = v_pad; a.t_out = z_out;
+    a.negate = negate ? 1 : 0; a.negmask = negmask;
+    if (g_ctx.opt_gram_nt) launch_gram_gv_nt<1>(H->nchunks, a, g_ctx.stream);
+    else launch_gram_gv_nt<0>(H->nchunks, a, g_ctx.stream);
+}
+
+// Gram form of launch_hmul: G rebuilt first when stale, then ONE launch — no slab reduction, no all-reduce.
+int32_t launch_gram_hmul(bh_hess* H, const double* v_pad, double* z_out, const CgState* state, int ev_index, bool negate,
+                         const int* negmask) {
+    BH_TRY(ensure_gram(H));
+    int slot = -1;
+    BH_TRY(profile_begin(H, ev_index, &slot));
+    launch_gram_gv(H, v_pad, z_out, state, negate, negmask);
+    if (slot >= 0) BH_HIP(hipEventRecord(H->ev[2 * slot + 1], g_ctx.stream));
+    BH_HIP(hipGetLastError());
+    return BH_OK;
+}
+
 // z_out (ld doubles, device) = sum over ranks of J_k'(W .* (J_k v)), v = v_pad (ld doubles, zero padded).
+// Gram form: z_out = G v (launch_gram_hmul).
 int32_t launch_hmul(bh_hess* H, const double* v_pad, double* z_out, const CgState* state, int ev_index, int reverse = 0,
                     bool negate = false, const int* negmask = nullptr) {
     BH_TRY(hess_ready(H));
+    if (H->form == BH_HESS_GRAM) return launch_gram_hmul(H, v_pad, z_out, state, ev_index, negate, negmask);
     const int64_t nrows = H->d + H->q_eff;
     if (multi_panel(H)) {
         BH_TRY(launch_jv_panels(H, v_pad, H->tbuf, nrows, state));
@@ -722,7 +826,7 @@ int32_t alloc_hess_common(bh_hess* H) {
     // partner for the RCCL form of the two-kernel iteration (there the H*p launch reads the previous launch's minima itself)
     BH_TRY(dev_alloc(&H->sq_partials, 3 * gmax));
     BH_TRY(dev_alloc(&H->scalar, 2));
-    H->stats.bytes_per_hmul = (multi_panel(H) ? 16.0 : 8.0) * (double)(H->d + H->q_eff) * (double)H->n + 16.0 * (double)H->n;
+    H->stats.bytes_per_hmul = hmul_bytes(H);
     return BH_OK;
 }
 
@@ -1352,6 +1456,7 @@ int32_t bh_set_option(const char* key, int64_t value) {
     }
     if (!strcmp(key, "pcg_batch")) { g_ctx.opt_batch = std::max<int64_t>(0, value); return BH_OK; }
     if (!strcmp(key, "pingpong")) { g_ctx.opt_pingpong = value ? 1 : 0; return BH_OK; }
+    if (!strcmp(key, "gram_nt")) { g_ctx.opt_gram_nt = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "proj_form")) { g_ctx.opt_proj_form = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "fold_init")) { g_ctx.opt_fold_init = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "cg_fused")) {
@@ -1804,7 +1909,52 @@ int32_t bh_hess_create_synthetic(bh_hess** out, int64_t d, int64_t n, int64_t ro
 
 int32_t bh_hess_set_mu(bh_hess* H, double mu) {
     if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
+    if (mu == H->mu) return BH_OK;          // the Julia shim calls this on every handle(H): never a rebuild
     H->mu = mu;
+    H->G_valid = false;                      // Gram form: rebuilt before the next product that reads G
+    return BH_OK;
+}
+
+static void gram_free(bh_hess* H) {
+    if (H->G || H->gpart) {
+        if (g_ctx.init) (void)hipStreamSynchronize(g_ctx.stream);   // launches still reading G may be queued
+        dev_free(H->G); dev_free(H->gpart);
+    }
+    H->G = nullptr; H->gpart = nullptr;
+    H->G_valid = false;
+}
+
+int32_t bh_hess_set_form(bh_hess* H, int32_t form) {
+    BH_REQUIRE_INIT();
+    if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
+    if (form != BH_HESS_IMPLICIT && form != BH_HESS_GRAM) return fail(BH_ERR_INVALID_ARG, "form is BH_HESS_IMPLICIT (0) or BH_HESS_GRAM (1)");
+    if (form == H->form) return BH_OK;
+    if (form == BH_HESS_GRAM) {
+        if (H->n > 16384) return fail(BH_ERR_UNSUPPORTED, "Gram form: n > 16384 (G would exceed 2 GiB)");
+        if (comm_active() && g_ctx.nranks > 1) return fail(BH_ERR_UNSUPPORTED, "Gram form: one rank only (no all-reduce of G)");
+        int slabs = 1;
+        int64_t slab_rows = 0;
+        gram_geometry(H, &slabs, &slab_rows);
+        int32_t rc = dev_alloc(&H->G, H->ld * H->ld);
+        if (rc == BH_OK && slabs > 1) rc = dev_alloc(&H->gpart, (int64_t)slabs * H->ld * H->ld);
+        if (rc != BH_OK) { gram_free(H); return rc; }        // the handle stays in the implicit form
+        H->gram_slabs = slabs;
+        H->gram_slab_rows = slab_rows;
+        H->G_valid = false;                                  // built before the first product that reads it (after the ingest)
+    } else {
+        gram_free(H);
+    }
+    H->form = form;
+    H->stats.bytes_per_hmul = hmul_bytes(H);
+    if (g_ctx.hw_note.H == H) g_ctx.hw_note = {};
+    if (g_ctx.gm_note.H == H) g_ctx.gm_note = {};
+    return BH_OK;
+}
+
+int32_t bh_hess_get_form(const bh_hess* H, int32_t* form, int64_t* gram_builds) {
+    if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
+    if (form) *form = H->form;
+    if (gram_builds) *gram_builds = H->gram_builds;
     return BH_OK;
 }
 
@@ -1827,6 +1977,7 @@ int32_t bh_hess_destroy(bh_hess* H) {
     }
     dev_free(H->vpad); dev_free(H->zpad); dev_free(H->upad); dev_free(H->tbuf); dev_free(H->timg); dev_free(H->timg_gen);
     dev_free(H->partials); dev_free(H->sq_partials); dev_free(H->scalar);
+    dev_free(H->G); dev_free(H->gpart);
     for (auto e : H->ev) if (e) (void)hipEventDestroy(e);
     delete H;
     return BH_OK;
@@ -2109,7 +2260,7 @@ static int launch_batch_size(const bh_hess* H) {
     if (g_ctx.opt_batch > 0) return (int)g_ctx.opt_batch;
     // rank-independent on purpose (see finish_hess_create): the even share of the rows over all ranks plus the full C
     // block, not this rank's own d + q_eff
-    const double rows = (double)((H->d_total + g_ctx.nranks - 1) / g_ctx.nranks + H->q);
+    const double rows = H->form == BH_HESS_GRAM ? (double)H->ld : (double)((H->d_total + g_ctx.nranks - 1) / g_ctx.nranks + H->q);
     const double est_us = (multi_panel(H) ? 16.0 : 8.0) * rows * (double)H->n / 7.0e6;      // ~7 TB/s streaming rate
     return est_us >= 100.0 ? 1 : est_us >= 40.0 ? 2 : 4;
 }
@@ -2168,7 +2319,9 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
     // p'Hp behind the vector, as in the box form below) and the update kernel, which then sums ONE slab — the all-reduced H*p:
     //   S(1) | R(1) AR(1) U(1) P(1) S(2) | ...   four kernels + the collective instead of seven, on the lock-step launch schedule.
     const bool rccl_gen = comm_active() && !use_peer_path() && fuse_gen;
-    if ((box || fuse_gen) && g_ctx.opt_cg_fused && rs_cfg >= 0 && cgp_supported(rs_cfg) && (!comm_active() || peer_fused || rccl_gen) && max_iter >= 1 &&
+    // Gram form: the fused and CGP shapes read J in their H*p launch — only the separate-kernel shape below goes through G
+    const bool gram = H->form == BH_HESS_GRAM;
+    if (!gram && (box || fuse_gen) && g_ctx.opt_cg_fused && rs_cfg >= 0 && cgp_supported(rs_cfg) && (!comm_active() || peer_fused || rccl_gen) && max_iter >= 1 &&
         (gp == c.g || n == n_pad)) {
         BH_TRY(hess_ready(H));
         H->stats.cg_kernels = (box ? 2 : (gen_linv ? 3 : 4)) + (rccl_gen ? 1 : 0);
@@ -2326,7 +2479,7 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
     // redoes it for the whole 32 KiB vector, the owners of a chunk store it), and the slab reduction packs this rank's share of
     // p'Hp behind the vector that goes through the all-reduce:  S(1) | R(1) AR(1) S(2) | R(2) AR(2) S(3) | ...
     // The launch schedule is the lock-step one of the three-kernel form below (decisions on "done by iteration k" only).
-    const bool rccl_fused = comm_active() && !use_peer_path() && box && g_ctx.opt_cg_fused && rs_cfg >= 0 && cgp3_supported(rs_cfg) &&
+    const bool rccl_fused = !gram && comm_active() && !use_peer_path() && box && g_ctx.opt_cg_fused && rs_cfg >= 0 && cgp3_supported(rs_cfg) &&
                             max_iter >= 1 && (gp == c.g || n == n_pad);
     H->stats.cg_kernels = 0;
     if (rccl_fused) {
@@ -3290,8 +3443,9 @@ int32_t bh_stats_reset(bh_hess* H) {
 
 int32_t bh_time_kernel(bh_hess* H, int32_t kind, int32_t reps, double* avg_ms) {
     BH_REQUIRE_INIT();
-    if (!H || !avg_ms || reps < 1 || kind < 0 || kind > 8) return fail(BH_ERR_INVALID_ARG, "bad argument");
+    if (!H || !avg_ms || reps < 1 || kind < 0 || kind > 10) return fail(BH_ERR_INVALID_ARG, "bad argument");
     BH_TRY(hess_ready(H));
+    if (kind >= 9 && H->form != BH_HESS_GRAM) return fail(BH_ERR_PRECONDITION, "bh_time_kernel(9, 10): the handle is not in the Gram form");
     if (kind == 7 && !comm_active()) return fail(BH_ERR_PRECONDITION, "bh_time_kernel(7): no communicator (bh_comm_init; BH_FORCE_COMM=1 for one rank)");
     struct EventPair {          // destroyed on every way out of this function
         hipEvent_t a = nullptr, b = nullptr;
@@ -3300,6 +3454,25 @@ int32_t bh_time_kernel(bh_hess* H, int32_t kind, int32_t reps, double* avg_ms) {
     BH_HIP(hipEventCreate(&evp.a));
     BH_HIP(hipEventCreate(&evp.b));
     const hipEvent_t e0 = evp.a, e1 = evp.b;
+    if (kind >= 9) {
+        // 9: a build of G (every launch a real build: gram_builds counts them); 10: one G·v launch (option "gram_nt" picks the loads)
+        BH_TRY(ensure_gram(H));
+        auto one = [&]() -> int32_t {
+            if (kind == 9) return launch_gram_build(H);
+            launch_gram_gv(H, H->vpad, H->zpad, nullptr, false, nullptr);
+            BH_HIP(hipGetLastError());
+            return BH_OK;
+        };
+        BH_TRY(one());                                        // warm-up
+        BH_HIP(hipEventRecord(e0, g_ctx.stream));
+        for (int i = 0; i < reps; ++i) BH_TRY(one());
+        BH_HIP(hipEventRecord(e1, g_ctx.stream));
+        BH_HIP(hipEventSynchronize(e1));
+        float ms = 0.f;
+        BH_HIP(hipEventElapsedTime(&ms, e0, e1));
+        *avg_ms = ms / reps;
+        return BH_OK;
+    }
     if (kind >= 7) {
         // 7: the all-reduce of one n-vector on the active communicator path; 8: everything an H*p does after its streaming
         // kernel (slab reduction + exchange).  Back-to-back launches between two events: all ranks must call this together.

@@ -24,3 +24,4 @@
 #include "bh_proj.hip.h"
 #include "bh_cauchy.hip.h"
 #include "bh_minor.hip.h"
+#include "bh_gngram.hip.h"

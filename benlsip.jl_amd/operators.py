@@ -133,6 +133,31 @@ class AlHessian:
     def handle(self):
         return self._h
 
+    _FORMS = {"implicit": _lib.BH_HESS_IMPLICIT, "gram": _lib.BH_HESS_GRAM}
+
+    def set_form(self, form):
+        """``bh_hess_set_form``: "implicit" (every product streams J) or "gram" (products read the explicit G = J'J + mu C'C,
+        built on first use and again after a change of mu).  vthv, jv, jtv, gradient and the row-space Cauchy search keep
+        reading J."""
+        if form not in self._FORMS:
+            raise ValueError("form is 'implicit' or 'gram', got %r" % (form,))
+        check(_lib.lib().bh_hess_set_form(self._h, self._FORMS[form]), "bh_hess_set_form")
+
+    def _get_form(self):
+        f, b = ct.c_int32(0), ct.c_int64(0)
+        check(_lib.lib().bh_hess_get_form(self._h, ct.byref(f), ct.byref(b)), "bh_hess_get_form")
+        return f.value, b.value
+
+    @property
+    def form(self):
+        """"implicit" or "gram" (``bh_hess_get_form``)."""
+        return {v: k for k, v in self._FORMS.items()}[self._get_form()[0]]
+
+    @property
+    def gram_builds(self):
+        """How many times G has been built on this handle (``bh_hess_get_form``)."""
+        return self._get_form()[1]
+
     def __mul__(self, v):
         return hmul(self, v)
 
@@ -162,7 +187,9 @@ class AlHessian:
         check(_lib.lib().bh_stats_reset(self._h), "bh_stats_reset")
 
     def time_kernel(self, kind, reps=20):
-        """Average hipEvent milliseconds of one launch: kind 0 = fused J'(Jp), 1 = J v, 2 = J'u, 3..6 = read-only stream probe with 1/2/4/8 workgroups per CU."""
+        """Average hipEvent milliseconds of one launch: kind 0 = fused J'(Jp), 1 = J v, 2 = J'u, 3..6 = read-only stream probe with 1/2/4/8 workgroups per CU,
+        7 = all-reduce of one n-vector, 8 = slab reduction (+ exchange) of an H*p; Gram form only (``set_form("gram")``): 9 = a build of G,
+        10 = one G·v launch (option "gram_nt" selects non-temporal loads)."""
         ms = ct.c_double(0.0)
         check(_lib.lib().bh_time_kernel(self._h, kind, reps, ct.byref(ms)), "bh_time_kernel")
         return ms.value

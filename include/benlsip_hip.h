@@ -151,8 +151,29 @@ int32_t bh_hess_wait(bh_hess* H);
  * element (i,j) = u(seed, i + j*d_total)/sqrt(d_total) * (colscale ? colscale[j] : 1), generated in HBM. */
 int32_t bh_hess_create_synthetic(bh_hess** out, int64_t d, int64_t n, int64_t row0, int64_t d_total,
                                  uint64_t seed, const double* colscale /* n or NULL */, double mu);
+/* Changing mu of the Gram form marks G stale (rebuilt before the next product that reads it); the same mu is a no-op. */
 int32_t bh_hess_set_mu(bh_hess* H, double mu);
 int32_t bh_hess_destroy(bh_hess* H);
+/* Form of the Gauss-Newton Hessian behind a handle.  Opt-in per handle; a new handle is BH_HESS_IMPLICIT.
+ *   BH_HESS_IMPLICIT  every product H*v = J'(Jv) + C'(mu C v) streams the whole image of J once (the default).
+ *   BH_HESS_GRAM      the explicit Gram matrix G = J'J + mu C'C (ld x ld doubles, exactly symmetric) is built on the fp64 matrix
+ *                     cores (gn_gram_mfma_kernel) before the first product that needs it — after an asynchronous ingest has
+ *                     finished, on the library stream, without a host synchronisation — and every such product is ONE G·v launch
+ *                     (8 n ld bytes instead of 8 (d+q) n; no slab reduction).  A new mu (bh_hess_set_mu) rebuilds it once.
+ *   Reading G in the Gram form: Base.:*(H, v) — src/basic_tralcnlss.jl:102-106 (bh_hmul, bh_hmul_dev), bh_hmul_add(_dev) and
+ *   bh_step_accumulate_dev, the H*p of projected_cg(...) — src/basic_tralcnlss.jl:690-764 (bh_pcg*, bh_minor_iterate*: always the
+ *   separate-kernel CG shape, stats.cg_kernels = 0, pHp = dot(p, H*p) as the reference forms it at :723) and the H*d form of
+ *   cauchy_step(...) — src/basic_tralcnlss.jl:574-639 (cauchy_image = 0, or more linear equalities than its row-space form takes).
+ *   Still reading J: vthv(H, v) — src/basic_tralcnlss.jl:92-96 and bh_linesearch (||Jv||^2_W, never negative), bh_jv, bh_jtv,
+ *   bh_grad, and the row-space Cauchy search (cauchy_image = 1, up to 64 equalities).
+ * bh_hess_set_form: setting the current form is a no-op; BH_HESS_IMPLICIT frees G; BH_ERR_INVALID_ARG for another value;
+ * BH_ERR_UNSUPPORTED for n > 16384 (G would exceed 2 GiB) or while a communicator with more than one rank is active; a failed
+ * allocation returns BH_ERR_HIP and leaves the handle in the implicit form.  While the Gram form is on, stats.bytes_per_hmul is
+ * 8 n ld + 16 n.  bh_hess_get_form: the current form and how many times G has been built on this handle. */
+#define BH_HESS_IMPLICIT 0
+#define BH_HESS_GRAM     1
+int32_t bh_hess_set_form(bh_hess* H, int32_t form);
+int32_t bh_hess_get_form(const bh_hess* H, int32_t* form, int64_t* gram_builds);
 int32_t bh_hess_shape(const bh_hess* H, int64_t* d, int64_t* n, int64_t* q);
 
 /* Base.:*(H::AlHessian, v) — src/basic_tralcnlss.jl:102-106:  out = J'(Jv) + C'(mu C v). */
@@ -367,6 +388,8 @@ int32_t bh_stats_reset(bh_hess* H);
  *   "rs_variant"     [0] A/B geometries of the row-streaming kernel for 2048 < n <= 4096 (tools/kernel_ab.py)
  *   "blocks_per_cu"  [0] workgroups per CU of the row-streaming kernels (0: per-geometry default)
  *   "pingpong"       [0] alternate the sweep direction of J between consecutive H*p
+ *   "gram_nt"        [1] Gram form (bh_hess_set_form): G·v with non-temporal loads (1) or plain loads (0).  Although every product
+ *                        re-reads G, the non-temporal loads measured faster at every size (config 3: 21.9 against 22.4 us per launch)
  *   "blocks_per_cu" accepts 0..8 (the partial-slab buffers hold 8 workgroups per CU); anything else is BH_ERR_INVALID_ARG
  *   "comm_path"      [0 with BH_COMM=rccl|both, 1 with BH_COMM=ipc] which communicator carries the all-reduces: 0 = RCCL,
  *                        1 = the one-shot peer-buffer exchange fused into the slab reduction (needs BH_COMM=ipc or both)
@@ -382,7 +405,8 @@ int32_t bh_set_option(const char* key, int64_t value);
  * non-temporal loads and adds) with 1, 2, 4, 8 workgroups per CU: the practical single-read ceiling the kernels are
  * quoted against; 7 = the all-reduce of one n-vector on the active communicator path (every rank must call it together);
  * 8 = everything an H*p does after its streaming kernel (slab reduction + all-reduce; without a communicator: the slab
- * reduction alone).  Returns the average milliseconds per launch. */
+ * reduction alone); 9 = a build of the Gram matrix G (each one counted by bh_hess_get_form), 10 = one G·v launch — both
+ * BH_ERR_PRECONDITION unless the handle is in the Gram form (bh_hess_set_form).  Returns the average milliseconds per launch. */
 int32_t bh_time_kernel(bh_hess* H, int32_t kind, int32_t reps, double* avg_ms);
 /* Device self-test of the wave64 DPP/permlane reduction network (sum and NaN-propagating min). */
 int32_t bh_selftest(void);

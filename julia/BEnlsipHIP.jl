@@ -61,10 +61,24 @@ function handle(H::BEnlsip.AlHessian{Float64})
     return h.ptr
 end
 
+# Explicit Gram form of the Hessian (bh_hess_set_form, INTEGRATION.md): opt-in, like resident_inner_step!.  When on, the methods
+# below that multiply by H (*, projected_cg, minor_iterate, inner_step) ask for G = J'J + mu C'C on the handle; the library
+# builds it once per J (and once more per new mu) and every later product reads G instead of J.  vthv, the gradient and
+# least_squares_multipliers' throw-away image keep the implicit form.
+#     BEnlsipHIP.gram_hessian!(true)
+const GRAM_HESSIAN = Ref(false)
+gram_hessian!(flag::Bool = true) = (GRAM_HESSIAN[] = flag)
+
+function product_handle(H::BEnlsip.AlHessian{Float64})
+    h = handle(H)
+    GRAM_HESSIAN[] && check(ccall((:bh_hess_set_form, libbh), Int32, (Ptr{Cvoid}, Int32), h, 1), "bh_hess_set_form")   # BH_HESS_GRAM
+    return h
+end
+
 # Base.:*(H, v) — src/basic_tralcnlss.jl:102-106
 function Base.:*(H::BEnlsip.AlHessian{Float64}, v::Vector{Float64})
     out = Vector{Float64}(undef, size(H.J, 2))
-    check(ccall((:bh_hmul, libbh), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), handle(H), v, out), "bh_hmul")
+    check(ccall((:bh_hmul, libbh), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), product_handle(H), v, out), "bh_hmul")
     return out
 end
 
@@ -127,7 +141,7 @@ function BEnlsip.projected_cg(g_minor::Vector{Float64}, H::BEnlsip.AlHessian{Flo
     check(ccall((:bh_pcg, libbh), Int32,
                 (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Float64, Float64,
                  Ptr{Float64}, Ref{Int32}, Ref{Int32}, Ptr{Float64}, Int64, Ref{Int32}),
-                handle(H), handle(lincons), g_minor, w_l, w_u, kappa2, atol, 1e-10,
+                product_handle(H), handle(lincons), g_minor, w_l, w_u, kappa2, atol, 1e-10,
                 w, status, iters, C_NULL, 0, nh), "bh_pcg")
     # 0..3 = CG_status (:12); 4 = the reference's `nothing` (iterations exhausted or max_iter == 0, :753-761)
     return w, (status[] == 4 ? nothing : BEnlsip.CG_status(status[]))
@@ -143,7 +157,7 @@ function BEnlsip.minor_iterate(x::Vector{Float64}, s::Vector{Float64}, g_model::
     check(ccall((:bh_minor_iterate, libbh), Int32,
                 (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Float64,
                  Float64, Float64, Ptr{Float64}, Ref{Int32}, Ref{Int32}, Ref{Int32}, Ref{Float64}),
-                handle(H), handle(lincons), x, s, g_model, lincons.xlow, lincons.xupp, delta, kappa2,
+                product_handle(H), handle(lincons), x, s, g_model, lincons.xlow, lincons.xupp, delta, kappa2,
                 sqrt(eps(Float64)), 1e-10, w, status, iters, nh, alpha), "bh_minor_iterate")
     return w, (status[] == 4 ? nothing : BEnlsip.CG_status(status[]))
 end
@@ -224,7 +238,7 @@ function BEnlsip.inner_step(x::Vector{Float64}, g::Vector{Float64}, H::BEnlsip.A
         d
     end
     upload!(dv[:x], x); upload!(dv[:g], g)
-    hH, hP = handle(H), handle(lincons)
+    hH, hP = product_handle(H), handle(lincons)
     chunks = lincons.fixvars.chunks                                   # written in place: lincons.fixvars follows the device
     nbp = Ref{Int32}(0); nh = Ref{Int32}(0)
     check(ccall((:bh_cauchy_step_dev, libbh), Int32,

@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""The explicit Gram form of the Gauss-Newton Hessian (bh_hess_set_form) against the implicit one, on synthetic instances:
+build of G (ms, TFLOP/s of the useful lower-triangle flop 2 (d+q) n (n+1)/2), one G·v launch with and without non-temporal
+loads (us, GB/s of its 8 n ld bytes), us per CG iteration of projected_cg (bench instance, "ic" columns: long runs) in both
+forms, whole projected_cg on the "ic" variant, us per breakpoint of an H*d Cauchy search with mA = 96, and the break-even
+number of products per J.  (Not to be confused with tools/gram_timing.py, which times A_free A_free'.)
+
+    python tools/gn_gram_timing.py [--out FILE] [--quick]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import benlsip_jl_amd as bh  # noqa: E402
+
+LINES = []
+
+
+def say(s):
+    print(s, flush=True)
+    LINES.append(s)
+
+
+def pcg_us(H, cons, dv, reps):
+    """Average wall time of one device-resident projected_cg (bh_pcg_dev) and its iteration count."""
+    st, it, nh = bh.operators.projected_cg_dev(dv["g"], H, dv["wl"], dv["wu"], cons, 0.1, dv["w"])     # warm-up (and the build of G)
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        st, it, nh = bh.operators.projected_cg_dev(dv["g"], H, dv["wl"], dv["wu"], cons, 0.1, dv["w"])
+    return 1e6 * (time.perf_counter() - t0) / reps, int(st), it, nh
+
+
+def instance(d, n, kind):
+    syn = bh.synthetic
+    H = bh.AlHessian.synthetic(d, n, seed=1, colscale=syn.column_scale(n, kind), mu=10.0)
+    x, x_l, x_u, fix = syn.box_vectors(n, fix_every=8)
+    cons = bh.MixedConstraints(np.zeros((0, n)), None, fix, l=x_l, u=x_u)
+    g = H.jtv(syn.residual_rows(0, d))
+    w_l, w_u = syn.step_bounds(x, x_l, x_u, fix, syn.initial_tr(g))
+    dv = {k: bh.DeviceVector(n, v) for k, v in (("g", g), ("wl", w_l), ("wu", w_u))}
+    dv["w"] = bh.DeviceVector(n)
+    return H, cons, dv, dict(x=x, x_l=x_l, x_u=x_u, g=g)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--quick", action="store_true", help="config 2 and 3 only, no Cauchy search (rocprofv3 runs)")
+    args = ap.parse_args()
+    bh.init(0)
+    shapes = [("config 2", 8192, 1024), ("config 3", 65536, 4096)]
+    if not args.quick:
+        shapes += [("n = 8192", 32768, 8192), ("n = 16384", 16384, 16384)]
+    say("# tools/gn_gram_timing.py: explicit Gram form (bh_hess_set_form) vs implicit, one MI355X; times are hipEvent (kernels) or wall (calls)")
+    for label, d, n in shapes:
+        ld = (n + 15) // 16 * 16
+        H, cons, dv, _ = instance(d, n, 1)                  # "ic": columns scaled 10^(-3j/n), long CG runs
+        t_imp_hmul = 1e3 * H.time_kernel(0, reps=10)
+        us_imp, st_imp, it_imp, nh_imp = pcg_us(H, cons, dv, 3)
+        H.set_form("gram")
+        ms_build = H.time_kernel(9, reps=3)
+        flop = 2.0 * d * n * (n + 1) / 2
+        gv = {}
+        for nt in (0, 1):
+            bh.set_option("gram_nt", nt)
+            gv[nt] = 1e3 * H.time_kernel(10, reps=50)
+        bh.set_option("gram_nt", 1)                       # the default
+        us_gram, st_gram, it_gram, nh_gram = pcg_us(H, cons, dv, 3)
+        per_imp, per_gram = us_imp / max(nh_imp, 1), us_gram / max(nh_gram, 1)
+        say("%s (d = %d, n = %d, ic): build of G %.3f ms = %.1f TFLOP/s (useful lower-triangle flop %.3g); G·v %.1f us = %.0f GB/s plain, "
+            "%.1f us = %.0f GB/s non-temporal; implicit fused H*p %.1f us"
+            % (label, d, n, ms_build, flop / (ms_build * 1e-3) / 1e12, flop, gv[0], 8.0 * n * ld / (gv[0] * 1e-6) / 1e9, gv[1],
+               8.0 * n * ld / (gv[1] * 1e-6) / 1e9, t_imp_hmul))
+        say("    projected_cg (bh_pcg_dev): implicit %.1f us, status %d, %d iterations, %d H*p = %.1f us per H*p; Gram %.1f us, status %d, "
+            "%d iterations, %d H*p = %.1f us per H*p  (%.2fx per iteration)"
+            % (us_imp, st_imp, it_imp, nh_imp, per_imp, us_gram, st_gram, it_gram, nh_gram, per_gram, per_imp / per_gram))
+        saved = per_imp - per_gram
+        say("    break-even: the build (%.3f ms) pays for itself after %s products per J (saving %.1f us per CG iteration)"
+            % (ms_build, "%.0f" % (1e3 * ms_build / saved) if saved > 0 else "never", saved))
+        H.close()
+    if args.quick:
+        return
+    # Cauchy search with 96 linear equalities at config-3 scale: one H*d per breakpoint (the row-space form stops at 64)
+    syn = bh.synthetic
+    d, n, mA = 65536, 4096, 96
+    H, cons0, dv, v = instance(d, n, 0)
+    A = syn.splitmix_uniform(4, np.arange(mA * n)).reshape((mA, n), order="F")
+    for form in ("implicit", "gram"):
+        H.set_form(form)
+        cons = bh.MixedConstraints(A, None, None, l=v["x_l"], u=v["x_u"])
+        delta = 1.0 * syn.initial_tr(v["g"])
+        bh.cauchy_step(v["x"], v["g"], H, cons, delta)
+        cons = bh.MixedConstraints(A, None, None, l=v["x_l"], u=v["x_u"])
+        t0 = time.perf_counter()
+        s, info = bh.cauchy_step(v["x"], v["g"], H, cons, delta, full_output=True)
+        el = time.perf_counter() - t0
+        say("cauchy_step config 3, mA = 96, %s form: %d breakpoints, %d passes, %.2f ms, %.1f us per pass, |s| = %.12e"
+            % (form, info["n_breakpoints"], info["n_hmul"], 1e3 * el, 1e6 * el / max(info["n_hmul"], 1), np.linalg.norm(s)))
+    H.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(LINES) + "\n")
+
+
+if __name__ == "__main__":
+    main()
