@@ -24,7 +24,7 @@ EXPORTS = [
     "bh_hmul", "bh_vthv", "bh_jv", "bh_jtv", "bh_hmul_dev", "bh_jv_dev", "bh_jtv_dev",
     "bh_proj_create", "bh_proj_set_active", "bh_proj_destroy", "bh_proj_shape", "bh_project", "bh_project_dev",
     "bh_left_mul", "bh_left_mul_tr",
-    "bh_pcg", "bh_pcg_dev", "bh_pcg_tie_info", "bh_resid_sqnorm", "bh_factor_to_boundary", "bh_minor_iterate", "bh_linesearch", "bh_grad", "bh_hmul_add", "bh_cauchy_step",
+    "bh_pcg", "bh_pcg_dev", "bh_pcg_tie_info", "bh_resid_sqnorm", "bh_factor_to_boundary", "bh_minor_iterate", "bh_linesearch", "bh_grad", "bh_hmul_add", "bh_cauchy_step", "bh_cauchy_info",
     "bh_cauchy_step_dev", "bh_minor_iterate_dev", "bh_linesearch_dev", "bh_grad_dev", "bh_hmul_add_dev", "bh_step_accumulate_dev",
     "bh_proj_update_active_dev", "bh_reduced_gradient_norm_dev", "bh_model_reduction_dev",
     "bh_dev_alloc", "bh_dev_free", "bh_dev_upload", "bh_dev_download", "bh_stats", "bh_stats_reset",
@@ -99,6 +99,7 @@ _PROTOS = {
     "bh_linesearch": ([_vp, _vp, _vp, _vp, _vp, _vp, _dp], _i32),
     "bh_cauchy_step": ([_vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _vp, C.POINTER(_i32), C.POINTER(_i32)], _i32),
     "bh_grad": ([_vp, _vp, _vp, _vp], _i32),
+    "bh_cauchy_info": ([_vp, C.POINTER(_i32), C.POINTER(_i32)], _i32),
     "bh_cauchy_step_dev": ([_vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _vp, C.POINTER(_i32), C.POINTER(_i32)], _i32),
     "bh_minor_iterate_dev": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _f64, _vp, C.POINTER(_i32), C.POINTER(_i32),
                              C.POINTER(_i32), _dp], _i32),

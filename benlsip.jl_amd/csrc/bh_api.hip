@@ -25,6 +25,12 @@
 
 using namespace bh;
 
+// Every kernel launch of the library goes through hipLaunchKernelGGL in this translation unit: count them (bh_cauchy_info reports
+// how many a search enqueued).
+static uint64_t g_kernel_launches = 0;
+#undef hipLaunchKernelGGL
+#define hipLaunchKernelGGL(kernelName, ...) do { ++g_kernel_launches; hipLaunchKernelGGLInternal((kernelName), __VA_ARGS__); } while (0)
+
 // ------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------
@@ -110,6 +116,7 @@ struct Ctx {
     int64_t opt_cauchy_image = 1;
     int64_t opt_cauchy_image_max_ma = 64;   // ... and with up to this many linear equalities (0..64)
     int64_t opt_cauchy_fused = 1;           // box constraints, one rank, row-space form: ONE kernel per breakpoint (cauchy_fused_kernel)
+    int64_t opt_cauchy_gram = 0;            // Gram-form handle, box constraints, one rank: the whole search from G in one launch (cauchy_gram_kernel)
     int64_t opt_cauchy_fused_grid = 0;      // experiment: workgroups of cauchy_fused_kernel (0: one row per thread up to kCauchyFusedGrid)
     int64_t opt_linv_refine = 1;            // explicit-inverse projection (three-kernel CG iteration): one step of iterative refinement of y
     int64_t opt_cauchy_gemm = 1;            // B = J D A' of that form in one sweep on the matrix cores (0: mA J v sweeps over masked rows of A)
@@ -441,6 +448,8 @@ struct bh_proj {
     double* tpart = nullptr;       // (ldA/32 + 1) x mA: per-workgroup partials of A_free r (three- / four-kernel CG iteration)
     double* W = nullptr;           // 2 x 64 x 64: [Linv | Linv'] of the reduced factor, mA <= 64 (tri_inv_small_kernel)
     bool linv_valid = false;       // W belongs to the current Lr
+    int last_cauchy_form = -1;     // bh_cauchy_info: form of the previous bh_cauchy_step on this handle (-1: none yet) ...
+    int last_cauchy_launches = 0;  // ... and the kernels it enqueued
     int last_cauchy_passes = 0;    // passes of the previous bh_cauchy_step on this handle (decides whether 1 + mA set-up sweeps pay off)
     bool reduced = false;          // form used by bh_project / bh_pcg for the current active set
     bool M_valid = false;          // M = A_free A_free' for the CURRENT active set (false after factor-only downdates)
@@ -1472,6 +1481,7 @@ int32_t bh_set_option(const char* key, int64_t value) {
     if (!strcmp(key, "gram_mfma")) { g_ctx.opt_gram_mfma = value; return BH_OK; }
     if (!strcmp(key, "chol_downdate")) { g_ctx.opt_chol_downdate = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "cauchy_image")) { g_ctx.opt_cauchy_image = value ? 1 : 0; return BH_OK; }
+    if (!strcmp(key, "cauchy_gram")) { g_ctx.opt_cauchy_gram = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "cauchy_fused")) { g_ctx.opt_cauchy_fused = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "cauchy_fused_grid")) { g_ctx.opt_cauchy_fused_grid = std::min<int64_t>(std::max<int64_t>(0, value), kCauchyFusedGrid); return BH_OK; }
     if (!strcmp(key, "linv_refine")) { g_ctx.opt_linv_refine = value ? 1 : 0; return BH_OK; }
@@ -3149,6 +3159,7 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     const int64_t n = H->n;
     if (n + 1 >= 0xfffff) return fail(BH_ERR_UNSUPPORTED, "n exceeds the 20-bit pass counter of the progress word");
     const int mA = (int)P->mA;
+    const uint64_t launches_in = g_kernel_launches;
     BH_TRY(ensure_cg_workspace(H->ld, 0));
     CgWorkspace& c = g_ctx.cg;
     hipStream_t s = g_ctx.stream;
@@ -3177,7 +3188,10 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     // (several ranks: every rank keeps t_d, t_s for ITS rows; the two sums are all-reduced before the replicated advance kernel)
     // With linear equalities the form costs 1 + mA J v sweeps up front: always used up to cauchy_image_max_ma rows; up to 64 rows when
     // the previous search on this handle took more than 4 (1 + mA) passes (consecutive searches of a solve behave alike).
-    const bool image = g_ctx.opt_cauchy_image != 0 &&
+    // Gram-form handle, box constraints, one rank, option "cauchy_gram": init -> G d -> cauchy_gram_kernel, the whole search in one
+    // launch (bh_cauchygram.hip.h).  Any other case takes the path it takes without the option.
+    const bool gram_search = g_ctx.opt_cauchy_gram != 0 && H->form == BH_HESS_GRAM && mA == 0 && !comm_active();
+    const bool image = !gram_search && g_ctx.opt_cauchy_image != 0 &&
                        (mA == 0 || mA <= g_ctx.opt_cauchy_image_max_ma || (mA <= 64 && P->last_cauchy_passes > 4 * (1 + mA)));
     const bool image_gen = image && mA > 0;
     // ... and there ONE kernel per breakpoint: the decision of pass k-1 in the prologue of the row kernel of pass k (cauchy_fused_kernel)
@@ -3328,6 +3342,16 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
         return BH_OK;
     };
     MirrorWord mw{};
+    if (gram_search) {
+        BH_TRY(launch_hmul(H, c.p, c.Hp, c.d_state, -1));           // Hd = H*d    :609  (rebuilds G first when it is stale)
+        H->stats.n_hmul += 1;
+        CauchyGramArgs ga{};
+        ga.c = a; ga.G = H->G; ga.ld = H->ld;
+        if (n <= 8 * CA_T) hipLaunchKernelGGL(cauchy_gram_kernel<true>, dim3(1), dim3(CA_T), 0, s, ga);
+        else hipLaunchKernelGGL(cauchy_gram_kernel<false>, dim3(1), dim3(CA_T), 0, s, ga);
+        BH_HIP(hipGetLastError());
+        launched = max_pass;                                        // the kernel publishes once, when its loop has ended
+    }
     // image-space passes take ~17 us: keep a deeper queue ahead of the GPU (over RCCL every over-launched pass costs a collective)
     const int batch = !image ? launch_batch_size(H) : (comm_active() && !use_peer_path()) ? 4 : 8;
     // (fused form: launch k carries decision k-1, so `launched` launches stand for launched - 1 passes)
@@ -3342,8 +3366,8 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     // Same launch-ahead schedule and the same rank-independent exit predicate as pcg_run (mirror: status field = error
     // flag, iter field = breakpoints, n_hmul = passes run).
     auto done_by = [&](int target) { return mw.done && mw.n_hmul <= target; };
-    BH_TRY(launch_batch(2 + off));
-    while (true) {
+    if (!gram_search) BH_TRY(launch_batch(2 + off));
+    while (!gram_search) {
         const int target = launched - off;
         const bool more = launched < max_launch;
         if (more) BH_TRY(launch_batch(batch));
@@ -3355,8 +3379,10 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     BH_TRY(fetch_vec(s_out, fused ? sbuf[mw.n_hmul & 1] : c.w, n, dev));
     int info_host = 0;
     BH_TRY(adopt_device_mask(P, fix_chunks_out, &info_host));     // drains the stream; canonical fixrank / fixidx, P->nfix
-    if (!image) H->stats.n_hmul += mw.n_hmul;                  // (image-space search: passes, not sweeps over J)
+    if (!image && !gram_search) H->stats.n_hmul += mw.n_hmul;  // (image-space search: passes, not sweeps over J)
     P->last_cauchy_passes = mw.n_hmul;
+    P->last_cauchy_form = gram_search ? 3 : !image ? 0 : image_gen ? 2 : 1;
+    P->last_cauchy_launches = (int)(g_kernel_launches - launches_in);
     if (!mw.done) return fail(BH_ERR_HIP, "internal: Cauchy loop did not terminate");
     if (n_breakpoints) *n_breakpoints = mw.iter;
     if (n_hmul_out) *n_hmul_out = mw.n_hmul;
@@ -3374,6 +3400,15 @@ int32_t bh_cauchy_step(bh_hess* H, bh_proj* P, const double* x, const double* g,
 int32_t bh_cauchy_step_dev(bh_hess* H, bh_proj* P, const double* x_dev, const double* g_dev, const double* xlow_dev, const double* xupp_dev,
                            double delta, double* s_out_dev, uint64_t* fix_chunks_out, int32_t* n_breakpoints, int32_t* n_hmul_out) {
     return cauchy_impl(H, P, x_dev, g_dev, xlow_dev, xupp_dev, delta, s_out_dev, fix_chunks_out, n_breakpoints, n_hmul_out, true);
+}
+
+int32_t bh_cauchy_info(const bh_proj* P, int32_t* form, int32_t* n_launches) {
+    BH_REQUIRE_INIT();
+    if (!P) return fail(BH_ERR_INVALID_ARG, "NULL handle");
+    if (P->last_cauchy_form < 0) return fail(BH_ERR_PRECONDITION, "bh_cauchy_info: no bh_cauchy_step on this handle yet");
+    if (form) *form = P->last_cauchy_form;
+    if (n_launches) *n_launches = P->last_cauchy_launches;
+    return BH_OK;
 }
 
 int32_t bh_factor_to_boundary(const double* p, const double* w, const double* w_l, const double* w_u, int64_t n, double atol,

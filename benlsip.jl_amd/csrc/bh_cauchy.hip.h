@@ -332,6 +332,34 @@ __global__ __launch_bounds__(256) void cauchy_image_kernel(CauchyImgArgs a) {
     if (threadIdx.x == 0) { a.part[blockIdx.x] = acc[0]; a.part[gridDim.x + blockIdx.x] = acc[1]; }
 }
 
+// next_breakpoint (:536-562) for one free variable: the step at which it meets its bound along d.  d_i == 0 (and NaN) gives Inf.
+__device__ __forceinline__ double cauchy_breakpoint_theta(double di, double si, double li, double ui) {
+    double t = __longlong_as_double(0x7ff0000000000000ll);
+    if (di < 0.0) t = __ddiv_rn(__dsub_rn(li, si), di);            // :549
+    else if (di > 0.0) t = __ddiv_rn(__dsub_rn(ui, si), di);       // :551
+    return t;
+}
+// Order of two arg-min candidates that met across lanes or waves: the smaller theta, the smaller index among equal thetas (:555).
+__device__ __forceinline__ bool cauchy_theta_before(double t2, int i2, double th, int ind) { return t2 < th || (t2 == th && i2 < ind); }
+
+// The while test (:615) and the three-way branch (:620-636) of one pass.  ind < 0: no breakpoint exists.
+struct CauchyDecision { int done, min_found, err, advance; double step, delta_t; };
+__device__ __forceinline__ CauchyDecision cauchy_decide(double phi_p, double phi_pp, double th, int ind, int nfix, int nmm) {
+    CauchyDecision q{0, 0, 0, 0, 0.0, 0.0};
+    q.delta_t = (phi_pp > 0.0) ? __ddiv_rn(-phi_p, phi_pp) : 0.0;     // :618
+    if (!(nfix < nmm)) {                                          // :615
+        q.done = 1;
+    } else if (phi_p >= 0.0) {                                    // :620
+        q.min_found = 1; q.done = 1;
+    } else if (phi_p < 0.0 && phi_pp > 0.0 && q.delta_t < th) {   // :622
+        q.step = q.delta_t; q.min_found = 1; q.done = 1;          // :625
+    } else {                                                      // :627
+        if (ind < 0) { q.err = 1; q.done = 1; }
+        else { q.step = th; q.advance = 1; }                      // :628
+    }
+    return q;
+}
+
 // progress word of the search: tag | error flag | done | breakpoints taken | passes run
 __device__ __forceinline__ void publish_cauchy_word(const CauchyArgs& a, int err, int done, int breakpoints, int passes) {
     if (a.mirror == nullptr) return;
@@ -422,9 +450,7 @@ __global__ __launch_bounds__(CA_T) void cauchy_advance_kernel(CauchyArgs a) {
             x3[1] = fma(di, hdi, x3[1]);
             x3[2] = fma(gv[k], di, x3[2]);
             if (fv[k] < 0) {                                          // :547
-                double t = INF;
-                if (di < 0.0) t = __ddiv_rn(__dsub_rn(lv[k], si), di);       // :549
-                else if (di > 0.0) t = __ddiv_rn(__dsub_rn(uv[k], si), di);  // :551
+                const double t = cauchy_breakpoint_theta(di, si, lv[k], uv[k]);
                 if (t < th) { th = t; ind = i; }                      // strict <: first minimiser in index order (:555)
             }
         }
@@ -437,7 +463,7 @@ __global__ __launch_bounds__(CA_T) void cauchy_advance_kernel(CauchyArgs a) {
     for (int off = 32; off >= 1; off >>= 1) {
         const double t2 = __shfl_xor(th, off);
         const int i2 = __shfl_xor(ind, off);
-        if (t2 < th || (t2 == th && i2 < ind)) { th = t2; ind = i2; }
+        if (cauchy_theta_before(t2, i2, th, ind)) { th = t2; ind = i2; }
     }
     if (lane == 0) {
         scratch[wave] = x3[0]; scratch[NW + wave] = x3[1]; scratch[2 * NW + wave] = x3[2];
@@ -450,26 +476,16 @@ __global__ __launch_bounds__(CA_T) void cauchy_advance_kernel(CauchyArgs a) {
     for (int w = 1; w < NW; ++w) {
         const double t2 = scratch[3 * NW + w];
         const int i2 = iscratch[w];
-        if (t2 < th || (t2 == th && i2 < ind)) { th = t2; ind = i2; }
+        if (cauchy_theta_before(t2, i2, th, ind)) { th = t2; ind = i2; }
     }
     if (img) { sums[0] = wave_sum(b0.fold_sum(a.img_part, a.img_G)); sums[1] = wave_sum(b1.fold_sum(a.img_part + a.img_G, a.img_G)); }
     if (ind == 0x7fffffff) ind = -1;                              // :544
 
     const double phi_p = __dadd_rn(sums[0], gd);                  // :610 / :634
     const double phi_pp = sums[1];                                // :611 / :635
-    int done = 0, min_found = 0, err = 0, advance = 0;
-    double step = 0.0;
-    const double delta_t = (phi_pp > 0.0) ? __ddiv_rn(-phi_p, phi_pp) : 0.0;     // :618
-    if (!(nfix < a.nmm)) {                                        // :615
-        done = 1;
-    } else if (phi_p >= 0.0) {                                    // :620
-        min_found = 1; done = 1;
-    } else if (phi_p < 0.0 && phi_pp > 0.0 && delta_t < th) {     // :622
-        step = delta_t; min_found = 1; done = 1;                  // :625
-    } else {                                                      // :627
-        if (ind < 0) { err = 1; done = 1; }
-        else { step = th; advance = 1; }                          // :628
-    }
+    const CauchyDecision q = cauchy_decide(phi_p, phi_pp, th, ind, nfix, a.nmm);          // :615-636
+    const int done = q.done, min_found = q.min_found, err = q.err, advance = q.advance;
+    const double step = q.step, delta_t = q.delta_t;
     if (step != 0.0 || advance) {
 #pragma unroll
         for (int k = 0; k < E; ++k) {                                 // the first batch: from registers
@@ -576,9 +592,7 @@ __global__ __launch_bounds__(CA_T) void cauchy_fused_kernel(CauchyFusedArgs a) {
             const double si = sv[k];
             gd = fma(gv[k], di, gd);
             if (!fixed) {                                             // :547
-                double t = INF;
-                if (di < 0.0) t = __ddiv_rn(__dsub_rn(lv[k], si), di);       // :549
-                else if (di > 0.0) t = __ddiv_rn(__dsub_rn(uv[k], si), di);  // :551
+                const double t = cauchy_breakpoint_theta(di, si, lv[k], uv[k]);
                 if (t < th) { th = t; ind = i; dbest = di; }          // strict <: first minimiser in index order (:555)
             }
         }
@@ -588,7 +602,7 @@ __global__ __launch_bounds__(CA_T) void cauchy_fused_kernel(CauchyFusedArgs a) {
     for (int off = 32; off >= 1; off >>= 1) {
         const double t2 = __shfl_xor(th, off), d2 = __shfl_xor(dbest, off);
         const int i2 = __shfl_xor(ind, off);
-        if (t2 < th || (t2 == th && i2 < ind)) { th = t2; ind = i2; dbest = d2; }
+        if (cauchy_theta_before(t2, i2, th, ind)) { th = t2; ind = i2; dbest = d2; }
     }
     if (lane == 0) { scratch[wave] = gd; scratch[NW + wave] = th; scratch[2 * NW + wave] = dbest; iscratch[wave] = ind; }
     __syncthreads();
@@ -598,25 +612,15 @@ __global__ __launch_bounds__(CA_T) void cauchy_fused_kernel(CauchyFusedArgs a) {
     for (int w = 1; w < NW; ++w) {
         const double t2 = scratch[NW + w];
         const int i2 = iscratch[w];
-        if (t2 < th || (t2 == th && i2 < ind)) { th = t2; ind = i2; dbest = scratch[2 * NW + w]; }
+        if (cauchy_theta_before(t2, i2, th, ind)) { th = t2; ind = i2; dbest = scratch[2 * NW + w]; }
     }
     const double shd = wave_sum(b0.fold_sum(a.part_in, a.Gin)), dhd = wave_sum(b1.fold_sum(a.part_in + a.Gin, a.Gin));
     if (ind == 0x7fffffff) ind = -1;                              // :544
     const double phi_p = __dadd_rn(shd, gd);                      // :610 / :634
     const double phi_pp = dhd;                                    // :611 / :635
-    int done = 0, err = 0, advance = 0;
-    double step = 0.0;
-    const double delta_t = (phi_pp > 0.0) ? __ddiv_rn(-phi_p, phi_pp) : 0.0;     // :618
-    if (!(nfix < a.nmm)) {                                        // :615
-        done = 1;
-    } else if (phi_p >= 0.0) {                                    // :620
-        done = 1;
-    } else if (phi_p < 0.0 && phi_pp > 0.0 && delta_t < th) {     // :622
-        step = delta_t; done = 1;                                 // :625
-    } else {                                                      // :627
-        if (ind < 0) { err = 1; done = 1; }
-        else { step = th; advance = 1; }                          // :628
-    }
+    const CauchyDecision q = cauchy_decide(phi_p, phi_pp, th, ind, nfix, a.nmm);          // :615-636
+    const int done = q.done, err = q.err, advance = q.advance;
+    const double step = q.step;
     // ---- s_c += step d (:625 / :628): the groups of 64 elements this workgroup owns ----------------------------------------------
     const bool move = (step != 0.0 || advance);
 #pragma unroll

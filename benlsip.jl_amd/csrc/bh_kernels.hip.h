@@ -23,5 +23,6 @@
 #include "bh_cgfuse.hip.h"
 #include "bh_proj.hip.h"
 #include "bh_cauchy.hip.h"
+#include "bh_cauchygram.hip.h"
 #include "bh_minor.hip.h"
 #include "bh_gngram.hip.h"

@@ -453,8 +453,17 @@ def cauchy_step(x, g, H, lincons, delta, full_output=False):
     lincons._chol = None
     lincons._dirty = False          # the device already holds this active set
     if full_output:
-        return s, {"n_breakpoints": nbp.value, "n_hmul": nh.value}
+        form, n_launches = cauchy_info(lincons)
+        return s, {"n_breakpoints": nbp.value, "n_hmul": nh.value, "form": form, "n_launches": n_launches}
     return s
+
+
+def cauchy_info(lincons):
+    """``bh_cauchy_info``: ``(form, n_launches)`` of the last ``cauchy_step`` on ``lincons`` — form 0 = one ``H*d`` per breakpoint,
+    1 = row space of ``J`` (box), 2 = row space of ``J`` with equalities, 3 = from ``G`` in one launch (option ``cauchy_gram``)."""
+    form, nl = ct.c_int32(-1), ct.c_int32(0)
+    check(_lib.lib().bh_cauchy_info(lincons._h, ct.byref(form), ct.byref(nl)), "bh_cauchy_info")
+    return form.value, nl.value
 
 
 def gradient(H, rx, y_bar=None):

@@ -163,9 +163,12 @@ int32_t bh_hess_destroy(bh_hess* H);
  *   Reading G in the Gram form: Base.:*(H, v) — src/basic_tralcnlss.jl:102-106 (bh_hmul, bh_hmul_dev), bh_hmul_add(_dev) and
  *   bh_step_accumulate_dev, the H*p of projected_cg(...) — src/basic_tralcnlss.jl:690-764 (bh_pcg*, bh_minor_iterate*: always the
  *   separate-kernel CG shape, stats.cg_kernels = 0, pHp = dot(p, H*p) as the reference forms it at :723) and the H*d form of
- *   cauchy_step(...) — src/basic_tralcnlss.jl:574-639 (cauchy_image = 0, or more linear equalities than its row-space form takes).
+ *   cauchy_step(...) — src/basic_tralcnlss.jl:574-639 (cauchy_image = 0, or more linear equalities than its row-space form takes);
+ *   with option "cauchy_gram" = 1 also the whole box-constrained search of cauchy_step(...) (no linear equalities, one rank):
+ *   Hd = G d once, then one row of G per breakpoint inside ONE launch (cauchy_gram_kernel).
  *   Still reading J: vthv(H, v) — src/basic_tralcnlss.jl:92-96 and bh_linesearch (||Jv||^2_W, never negative), bh_jv, bh_jtv,
- *   bh_grad, and the row-space Cauchy search (cauchy_image = 1, up to 64 equalities).
+ *   bh_grad, and the row-space Cauchy search (cauchy_image = 1, up to 64 equalities; with box constraints only while
+ *   "cauchy_gram" = 0).
  * bh_hess_set_form: setting the current form is a no-op; BH_HESS_IMPLICIT frees G; BH_ERR_INVALID_ARG for another value;
  * BH_ERR_UNSUPPORTED for n > 16384 (G would exceed 2 GiB) or while a communicator with more than one rank is active; a failed
  * allocation returns BH_ERR_HIP and leaves the handle in the implicit form.  While the Gram form is on, stats.bytes_per_hmul is
@@ -264,6 +267,11 @@ int32_t bh_linesearch(bh_hess* H, bh_proj* P, const double* g_model, const doubl
  * update lincons.fixvars (and its own factor, if it still needs one). */
 int32_t bh_cauchy_step(bh_hess* H, bh_proj* P, const double* x, const double* g, const double* xlow, const double* xupp,
                        double delta, double* s_out, uint64_t* fix_chunks_out, int32_t* n_breakpoints, int32_t* n_hmul);
+/* Form and launch count of the last bh_cauchy_step(_dev) on this bh_proj:
+ *   form 0 = one H*d per breakpoint, 1 = row space of J (box), 2 = row space of J with equalities, 3 = from G in one launch
+ *   n_launches = kernels enqueued by that call (over-launched prologue-only passes included).
+ * BH_ERR_PRECONDITION before the first search on the handle. */
+int32_t bh_cauchy_info(const bh_proj* P, int32_t* form, int32_t* n_launches);
 /* g = Jx'*rx + Cx'*y_bar — src/basic_tralcnlss.jl:45 (new_point), :74 (first_derivatives); r = this rank's d rows, y_bar has q entries. */
 int32_t bh_grad(bh_hess* H, const double* r, const double* ybar, double* g_out);
 /* dot(rx,rx) of the augmented-Lagrangian value mx = 0.5*dot(rx,rx) + dot(y,cx) + 0.5*mu*dot(cx,cx) — src/basic_tralcnlss.jl:44
@@ -376,6 +384,10 @@ int32_t bh_stats_reset(bh_hess* H);
  *                        previous search on the same bh_proj took more than 4 (1 + mA) passes
  *   "cauchy_fused"   [1] that search (box constraints, one rank) with ONE kernel per breakpoint: every workgroup of the row kernel redoes the
  *                        previous pass's decision in its prologue (s_c and the loop state are ping-pong buffers); 0: two kernels per pass
+ *   "cauchy_gram"    [0] bh_cauchy_step(_dev) on a handle in the Gram form (bh_hess_set_form), no linear equalities, one rank: the whole
+ *                        search in ONE launch from G (init -> G d -> cauchy_gram_kernel: Hd downdated by one row of G per breakpoint, the
+ *                        loop runs on the device; the launch count does not depend on the number of breakpoints).  Any other handle or
+ *                        constraint set takes the path it takes with 0.  bh_cauchy_info tells which form ran
  *   "cauchy_fused_grid" [0] workgroups of that kernel (0: one row per thread up to 256 workgroups; measured best — tools/scratch/cauchy_grid_sweep.py)
  *   "linv_refine"    [1] three-kernel CG iteration with linear equalities (cg_fused = 1): one step of iterative refinement behind the
  *                        explicit inverse of the factor (rho = t - A_free A_free' y, y += L^-T L^-1 rho), so that A_free v stays at the level

@@ -69,6 +69,16 @@ end
 const GRAM_HESSIAN = Ref(false)
 gram_hessian!(flag::Bool = true) = (GRAM_HESSIAN[] = flag)
 
+# Whole box-constrained Cauchy search from G in one launch (bh_set_option("cauchy_gram", 1), DESIGN.md §8 f-5): opt-in.  It only
+# has an effect together with BOTH gram_hessian!(true) (the handle must hold G) and device_cauchy_step!(true) or
+# resident_inner_step!(true) (cauchy_step must run on the device at all), and only without linear equalities on one rank; in every
+# other case the search takes the path it takes without it.
+#     BEnlsipHIP.gram_cauchy!(true)
+function gram_cauchy!(flag::Bool = true)
+    check(ccall((:bh_set_option, libbh), Int32, (Cstring, Int64), "cauchy_gram", flag ? 1 : 0), "bh_set_option(cauchy_gram)")
+    return flag
+end
+
 function product_handle(H::BEnlsip.AlHessian{Float64})
     h = handle(H)
     GRAM_HESSIAN[] && check(ccall((:bh_hess_set_form, libbh), Int32, (Ptr{Cvoid}, Int32), h, 1), "bh_hess_set_form")   # BH_HESS_GRAM
