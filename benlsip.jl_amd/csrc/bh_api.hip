@@ -101,9 +101,7 @@ struct Ctx {
     std::string detail;
     // options
     int64_t opt_blocks_per_cu = 0;   // 0 = per-config default
-    int64_t opt_variant = 0;         // kernel geometry variant for the 2048-chunk (n<=4096) class
     int64_t opt_batch = 0;           // CG iterations launched ahead of the host's done-flag poll; 0 = by problem size (auto_batch)
-    int64_t opt_chol_blocked = 1;    // mA > 64: blocked potrf/trsm/syrk chain (0: one-workgroup right-looking kernel)
     // Cauchy search, per breakpoint: 0 = downdate the Gram matrix A_free A_free' and refactor it (O(mA^3), the default: its
     // factor is as accurate as the reference's from-scratch rebuild), 1 = for mA > 64: rank-one downdate of the factor itself
     // (O(mA^2)), refreshed from scratch every kDowndateRefresh breakpoints.  Errors accumulate over the downdates — measured on the
@@ -117,7 +115,6 @@ struct Ctx {
     int64_t opt_cauchy_image_max_ma = 64;   // ... and with up to this many linear equalities (0..64)
     int64_t opt_cauchy_fused = 1;           // box constraints, one rank, row-space form: ONE kernel per breakpoint (cauchy_fused_kernel)
     int64_t opt_cauchy_gram = 0;            // Gram-form handle, box constraints, one rank: the whole search from G in one launch (cauchy_gram_kernel)
-    int64_t opt_cauchy_fused_grid = 0;      // experiment: workgroups of cauchy_fused_kernel (0: one row per thread up to kCauchyFusedGrid)
     int64_t opt_linv_refine = 1;            // explicit-inverse projection (three-kernel CG iteration): one step of iterative refinement of y
     int64_t opt_cauchy_gemm = 1;            // B = J D A' of that form in one sweep on the matrix cores (0: mA J v sweeps over masked rows of A)
     int64_t opt_gram_mfma = 1;       // A_free A_free': 1 = matrix cores when mA > 96, 2 = always, 0 = never (one wave per entry, VALU)
@@ -133,16 +130,11 @@ struct Ctx {
     struct { const void* H = nullptr; const double* s = nullptr; const double* g = nullptr; const double* gm = nullptr; } gm_note;
     int64_t opt_fold_init = 1;       // box CG: fold the initialisation into the first H*p / step launches
     int64_t opt_final_sync = 0;      // *_dev: always drain the stream before returning (1), or only wait for what the host is owed (0)
-    // the end-of-call wait of the host-pointer entry points: hipStreamSynchronize (0) or a mailbox seal + poll (1: A/B'd, SLOWER —
-    // a kernel behind a D2H DMA pays a cross-engine dependency: bh_pcg 0.667 -> 0.72 ms, bh_project 34 -> 45-50 us; kept as a switch)
-    int64_t opt_mbox_flush = 0;
     int64_t opt_host_copy_kernels = 1;   // host vectors of the host-pointer entry points: copy kernels on the mapped pinned arena (1) or DMA (0)
     int64_t opt_cg_fused = 1;        // box CG: two kernels per iteration (H*p with the p-update folded in + reduce/update) instead of three
     int64_t opt_proj_form = 1;       // 1: reduced mA x mA form (fast), 0: the reference's augmented mpp x mpp form
     int64_t opt_upload_chunk_mb = 64; // bh_hess_create_async: MiB of J per pipelined column chunk
     int64_t opt_ev_stride = 8;       // BH_FLAG_PROFILE: hipEvents around every opt_ev_stride-th H*p launch of a handle
-    int64_t opt_gram_nt = 1;         // Gram form: G·v with non-temporal loads (1, measured faster at every size: profiles/r04_gn_gram_timing.txt) or plain (0)
-    int64_t opt_pingpong = 0;        // alternate the sweep direction of J between consecutive H*p products (A/B: +1 % without nt loads, -0.2 % with)
     // RCCL
     void* rccl_lib = nullptr;
     ncclComm_t comm = nullptr;
@@ -247,17 +239,9 @@ const RsConfig kRsConfigs[] = {
     {256, 1, 8, 4},    // 1: nchunks <= 256   (n <= 512)
     {256, 2, 8, 2},    // 2: nchunks <= 512   (n <= 1024)   2 WGs/CU measured best (6.5 vs 6.0 TB/s at 4)
     {256, 4, 4, 2},    // 3: nchunks <= 1024  (n <= 2048)   2 WGs/CU measured best (6.6 vs 6.0 TB/s at 4)
-    {256, 8, 4, 1},    // 4: nchunks <= 2048  (n <= 4096)   variant 0 (measured best: 1 WG/CU, 128 KiB in flight)
+    {256, 8, 4, 1},    // 4: nchunks <= 2048  (n <= 4096)   measured best of nine geometries: 1 WG/CU, 128 KiB in flight
     {512, 8, 2, 1},    // 5: nchunks <= 4096  (n <= 8192)
-    {512, 4, 4, 1},    // 6: nchunks <= 2048  variant 1
-    {256, 8, 2, 1},    // 7: nchunks <= 2048  variant 2
-    {1024, 2, 4, 1},   // 8: nchunks <= 2048  variant 3
-    {512, 4, 2, 1},    // 9: nchunks <= 2048  variant 4
-    {256, 8, 4, 1},    // 10: nchunks <= 2048 variant 5 = variant 0 WITHOUT non-temporal loads of J (A/B: nt = +10 %)
-    {256, 8, 4, 2},    // 11: variant 6 = one register buffer (no prefetch), 2 WGs/CU
-    {256, 8, 3, 1},    // 12: variant 7 = R = 3 with prefetch
-    {256, 8, 6, 1},    // 13: variant 8 = R = 6, one register buffer
-    {512, 16, 1, 1},   // 14: nchunks <= 8192 (n <= 16384): one row per step; the fused mode parks v in LDS (VL)
+    {512, 16, 1, 1},   // 6: nchunks <= 8192  (n <= 16384): one row per step; the fused mode parks v in LDS (VL)
 };
 constexpr int64_t kMaxChunks = 8192;
 constexpr int64_t kMaxBlocksPerCu = 8;   // partial-slab capacity per handle: n_cu * kMaxBlocksPerCu workgroups (alloc_hess_common)
@@ -267,33 +251,21 @@ int pick_config(int nchunks) {
     if (nchunks <= 256) return 1;
     if (nchunks <= 512) return 2;
     if (nchunks <= 1024) return 3;
-    if (nchunks <= 2048) {
-        switch (g_ctx.opt_variant) {
-            case 1: return 6;
-            case 2: return 7;
-            case 3: return 8;
-            case 4: return 9;
-            case 5: return 10;
-            case 6: return 11;
-            case 7: return 12;
-            case 8: return 13;
-            default: return 4;
-        }
-    }
+    if (nchunks <= 2048) return 4;
     if (nchunks <= 4096) return 5;
-    return 14;
+    return 6;
 }
 
-template <int T, int CPT, int R, int NT = 1, int PF = 1>
+template <int T, int CPT, int R>
 void launch_rs_mode(int mode, const RowStreamArgs& a, int grid, hipStream_t s) {
     switch (mode) {
-        case MODE_JV: hipLaunchKernelGGL((row_stream_kernel<T, CPT, R, MODE_JV, NT, PF>), dim3(grid), dim3(T), 0, s, a); break;
-        case MODE_JTV: hipLaunchKernelGGL((row_stream_kernel<T, CPT, R, MODE_JTV, NT, PF>), dim3(grid), dim3(T), 0, s, a); break;
-        default: hipLaunchKernelGGL((row_stream_kernel<T, CPT, R, MODE_FUSED, NT, PF>), dim3(grid), dim3(T), 0, s, a); break;
+        case MODE_JV: hipLaunchKernelGGL((row_stream_kernel<T, CPT, R, MODE_JV>), dim3(grid), dim3(T), 0, s, a); break;
+        case MODE_JTV: hipLaunchKernelGGL((row_stream_kernel<T, CPT, R, MODE_JTV>), dim3(grid), dim3(T), 0, s, a); break;
+        default: hipLaunchKernelGGL((row_stream_kernel<T, CPT, R, MODE_FUSED>), dim3(grid), dim3(T), 0, s, a); break;
     }
 }
 
-// MODE_FUSED with the CG prologue (two-kernel box iteration); default geometries only.  CGP = 2: the launch expected to stop.
+// MODE_FUSED with the CG prologue (two-kernel box iteration).  CGP = 2: the launch expected to stop.
 template <int T, int CPT, int R>
 void launch_rs_cgp(const RowStreamArgs& a, int grid, hipStream_t s, bool expect_stop) {
     if (expect_stop) hipLaunchKernelGGL((row_stream_kernel<T, CPT, R, MODE_FUSED, 1, 1, 0, 2>), dim3(grid), dim3(T), 0, s, a);
@@ -322,15 +294,7 @@ void launch_row_stream(int cfg, int mode, const RowStreamArgs& a, int grid, hipS
         case 3: launch_rs_mode<256, 4, 4>(mode, a, grid, s); break;
         case 4: launch_rs_mode<256, 8, 4>(mode, a, grid, s); break;
         case 5: launch_rs_mode<512, 8, 2>(mode, a, grid, s); break;
-        case 6: launch_rs_mode<512, 4, 4>(mode, a, grid, s); break;
-        case 7: launch_rs_mode<256, 8, 2>(mode, a, grid, s); break;
-        case 8: launch_rs_mode<1024, 2, 4>(mode, a, grid, s); break;
-        case 10: launch_rs_mode<256, 8, 4, 0>(mode, a, grid, s); break;
-        case 11: launch_rs_mode<256, 8, 4, 1, 0>(mode, a, grid, s); break;
-        case 12: launch_rs_mode<256, 8, 3, 1, 1>(mode, a, grid, s); break;
-        case 13: launch_rs_mode<256, 8, 6, 1, 0>(mode, a, grid, s); break;
-        case 14: launch_rs_mode_vlds<512, 16, 1>(mode, a, grid, s); break;
-        default: launch_rs_mode<512, 4, 2>(mode, a, grid, s); break;
+        default: launch_rs_mode_vlds<512, 16, 1>(mode, a, grid, s); break;
     }
 }
 
@@ -347,7 +311,6 @@ void launch_row_stream_cgp3(int cfg, const RowStreamArgs& a, int grid, hipStream
     }
 }
 
-bool cgp_supported(int cfg) { return cfg <= 5 || cfg == 14; }
 void launch_row_stream_cgp(int cfg, const RowStreamArgs& a, int grid, hipStream_t s, bool expect_stop) {
     switch (cfg) {
         case 0: launch_rs_cgp<64, 1, 8>(a, grid, s, expect_stop); break;
@@ -689,37 +652,15 @@ int32_t ensure_gram(bh_hess* H) {
 }
 
 // G·v: row_stream_kernel in J·v mode over the G image (ld rows, every weight 1; the padding rows of G are zero, so z_out's
-// padding comes out zero).  NT = 1: non-temporal loads — faster than plain loads although G is re-read by every product
+// padding comes out zero).  Its non-temporal loads are faster than plain ones although G is re-read by every product
 // (config 3: 21.9 against 22.4 us; n = 8192: 78.3 against 86.5 us; profiles/r04_gn_gram_timing.txt).
-template <int NT>
-void launch_gram_gv_nt(int64_t nchunks, const RowStreamArgs& a, hipStream_t s) {
-    int cfg;
-    if (nchunks <= 64) cfg = 0;
-    else if (nchunks <= 256) cfg = 1;
-    else if (nchunks <= 512) cfg = 2;
-    else if (nchunks <= 1024) cfg = 3;
-    else if (nchunks <= 2048) cfg = 4;
-    else if (nchunks <= 4096) cfg = 5;
-    else cfg = 14;
-    const int grid = grid_for(cfg, a.nrows);
-    switch (cfg) {
-        case 0: hipLaunchKernelGGL((row_stream_kernel<64, 1, 8, MODE_JV, NT>), dim3(grid), dim3(64), 0, s, a); break;
-        case 1: hipLaunchKernelGGL((row_stream_kernel<256, 1, 8, MODE_JV, NT>), dim3(grid), dim3(256), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((row_stream_kernel<256, 2, 8, MODE_JV, NT>), dim3(grid), dim3(256), 0, s, a); break;
-        case 3: hipLaunchKernelGGL((row_stream_kernel<256, 4, 4, MODE_JV, NT>), dim3(grid), dim3(256), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((row_stream_kernel<256, 8, 4, MODE_JV, NT>), dim3(grid), dim3(256), 0, s, a); break;
-        case 5: hipLaunchKernelGGL((row_stream_kernel<512, 8, 2, MODE_JV, NT>), dim3(grid), dim3(512), 0, s, a); break;
-        default: hipLaunchKernelGGL((row_stream_kernel<512, 16, 1, MODE_JV, NT>), dim3(grid), dim3(512), 0, s, a); break;
-    }
-}
-
 void launch_gram_gv(bh_hess* H, const double* v_pad, double* z_out, const CgState* state, bool negate, const int* negmask) {
     RowStreamArgs a{};
     a.J = H->G; a.ld = H->ld; a.nrows = H->ld; a.d_rows = H->ld; a.nchunks = H->nchunks; a.mu = 1.0; a.state = state;
     a.v = v_pad; a.t_out = z_out;
     a.negate = negate ? 1 : 0; a.negmask = negmask;
-    if (g_ctx.opt_gram_nt) launch_gram_gv_nt<1>(H->nchunks, a, g_ctx.stream);
-    else launch_gram_gv_nt<0>(H->nchunks, a, g_ctx.stream);
+    const int cfg = pick_config(H->nchunks);
+    launch_row_stream(cfg, MODE_JV, a, grid_for(cfg, a.nrows), g_ctx.stream);
 }
 
 // Gram form of launch_hmul: G rebuilt first when stale, then ONE launch — no slab reduction, no all-reduce.
@@ -736,8 +677,8 @@ int32_t launch_gram_hmul(bh_hess* H, const double* v_pad, double* z_out, const C
 
 // z_out (ld doubles, device) = sum over ranks of J_k'(W .* (J_k v)), v = v_pad (ld doubles, zero padded).
 // Gram form: z_out = G v (launch_gram_hmul).
-int32_t launch_hmul(bh_hess* H, const double* v_pad, double* z_out, const CgState* state, int ev_index, int reverse = 0,
-                    bool negate = false, const int* negmask = nullptr) {
+int32_t launch_hmul(bh_hess* H, const double* v_pad, double* z_out, const CgState* state, int ev_index, bool negate = false,
+                    const int* negmask = nullptr) {
     BH_TRY(hess_ready(H));
     if (H->form == BH_HESS_GRAM) return launch_gram_hmul(H, v_pad, z_out, state, ev_index, negate, negmask);
     const int64_t nrows = H->d + H->q_eff;
@@ -749,7 +690,7 @@ int32_t launch_hmul(bh_hess* H, const double* v_pad, double* z_out, const CgStat
     const int cfg = pick_config(H->nchunks);
     const int grid = grid_for(cfg, nrows);
     RowStreamArgs a = rs_args(H, nrows, state);
-    a.v = v_pad; a.partials = H->partials; a.reverse = reverse;
+    a.v = v_pad; a.partials = H->partials;
     a.negate = negate ? 1 : 0; a.negmask = negmask;
     // BH_FLAG_PROFILE: hipEvents around every opt_ev_stride-th (default 8th) H*p launch of this handle, counted ACROSS calls
     // (an event pair costs ~10 us of stream time; timing every launch would slow the loop it measures by 3 %).
@@ -827,7 +768,7 @@ int32_t alloc_hess_common(bh_hess* H) {
     if (multi_panel(H)) BH_TRY(dev_alloc(&H->tbuf, std::max<int64_t>(rows, 1)));
     BH_HIP(hipMemsetAsync(H->vpad, 0, H->ld * sizeof(double), g_ctx.stream));
     BH_HIP(hipMemsetAsync(H->zpad, 0, H->ld * sizeof(double), g_ctx.stream));
-    // partial slabs: enough for the largest grid any variant may use
+    // partial slabs: enough for the largest grid the option blocks_per_cu may ask for
     int64_t gmax = (int64_t)g_ctx.n_cu * kMaxBlocksPerCu;
     H->g_cap = (int)gmax;
     BH_TRY(dev_alloc(&H->partials, gmax * H->ld));
@@ -1152,15 +1093,15 @@ void pin_arena_deliver() {
 }
 
 // Wait until everything enqueued has completed, deliver the results parked in the pinned arena, reset the arena:
-// hipStreamSynchronize.  (Experiment switch mailbox_flush = 1: a seal in the mailbox + a poll instead.  It pays where no DMA
-// precedes it — the device-pointer entry points use it through mbox_seal_and_wait — but behind a D2H DMA the seal kernel
-// waits for a cross-engine dependency that costs more than the synchronize it replaces: measured slower, off by default.)
+// hipStreamSynchronize, or a seal in the mailbox + a poll where no DMA precedes it (the device-pointer entry points use that
+// through mbox_seal_and_wait).  Behind a D2H DMA the seal kernel waits for a cross-engine dependency that costs more than the
+// synchronize it replaces (A/B'd: bh_pcg 0.667 -> 0.72 ms, bh_project 34 -> 45-50 us), so there it stays a synchronize.
 int32_t sync_flush() {
     // No DMA engine involved since the last flush (the host vectors travelled through arena_copy_kernel): a seal + poll ends
-    // the call without a hipStreamSynchronize.  (mailbox_flush = 1 forces the seal path also behind DMAs: measured slower.)
+    // the call without a hipStreamSynchronize.
     const bool kernels_only = arena_kernels() && !g_pin.dma;
     g_pin.dma = false;
-    if (!g_ctx.opt_final_sync && (g_ctx.opt_mbox_flush || kernels_only) && g_ctx.mbox_h != nullptr) {
+    if (!g_ctx.opt_final_sync && kernels_only && g_ctx.mbox_h != nullptr) {
         unsigned long long seq = 0;
         BH_TRY(mbox_seal(&seq));
         BH_TRY(mbox_poll(seq));
@@ -1212,7 +1153,7 @@ int32_t ensure_reduced_buffers(bh_proj* P) {
 
 // Lr = chol(M) (lower, column-major mA x mA).  mA <= 64: one launch of the register-panel kernel (+ reciprocal diagonal
 // after the matrix for trsv_small_kernel).  Larger: blocked right-looking — per 64-column panel potrf on the diagonal
-// block, trsm for the rows below it, syrk for the trailing matrix (3 launches per panel; 1.6 ms -> ~0.3 ms at mA = 256).
+// block, trsm for the rows below it, syrk for the trailing matrix (3 launches per panel; ~0.3 ms at mA = 256, against 1.6 ms for one right-looking workgroup).
 int32_t launch_chol(bh_proj* P, const CgState* gate) {
     const int mA = (int)P->mA;
     hipStream_t s = g_ctx.stream;
@@ -1220,11 +1161,6 @@ int32_t launch_chol(bh_proj* P, const CgState* gate) {
     if (mA <= 64) {
         hipLaunchKernelGGL(chol_small_kernel, dim3(1), dim3(256), 0, s, (const double*)P->M, (int64_t)mA, P->Lr, (int64_t)mA, mA,
                            P->Lr + (int64_t)mA * mA, P->info, 0, gate == nullptr ? 1 : 0, gate);
-        BH_HIP(hipGetLastError());
-        return BH_OK;
-    }
-    if (!g_ctx.opt_chol_blocked) {
-        hipLaunchKernelGGL(chol_lower_kernel, dim3(1), dim3(CG_T), 0, s, (const double*)P->M, P->Lr, mA, P->info, gate);
         BH_HIP(hipGetLastError());
         return BH_OK;
     }
@@ -1393,12 +1329,9 @@ int32_t bh_init(int32_t device, int32_t flags) {
     g_ctx.stream = g_ctx.own_stream;
     BH_TRY(dev_alloc(&g_ctx.scratch_dev, 1024));
     BH_TRY(mbox_ensure());
-    if (const char* s = getenv("BH_MAILBOX_FLUSH")) g_ctx.opt_mbox_flush = atoll(s) ? 1 : 0;
     if (const char* s = getenv("BH_HOST_COPY_KERNELS")) g_ctx.opt_host_copy_kernels = atoll(s) ? 1 : 0;
-    if (const char* s = getenv("BH_RS_VARIANT")) g_ctx.opt_variant = atoll(s);
     if (const char* s = getenv("BH_BLOCKS_PER_CU")) g_ctx.opt_blocks_per_cu = std::min<int64_t>(std::max<int64_t>(0, atoll(s)), kMaxBlocksPerCu);
     if (const char* s = getenv("BH_PCG_BATCH")) g_ctx.opt_batch = std::max<int64_t>(0, atoll(s));
-    if (const char* s = getenv("BH_PINGPONG")) g_ctx.opt_pingpong = atoll(s) ? 1 : 0;
     if (const char* s = getenv("BH_PROJ_FORM")) g_ctx.opt_proj_form = atoll(s) ? 1 : 0;
     if (const char* s = getenv("BH_CG_FUSED")) g_ctx.opt_cg_fused = std::min<int64_t>(std::max<int64_t>(0, atoll(s)), 2);
     if (const char* s = getenv("BH_FINAL_SYNC")) g_ctx.opt_final_sync = atoll(s) ? 1 : 0;
@@ -1457,15 +1390,12 @@ int32_t bh_device_info(char* name_out, int64_t name_cap, int32_t* n_cu, char* ar
 
 int32_t bh_set_option(const char* key, int64_t value) {
     if (!key) return fail(BH_ERR_INVALID_ARG, "NULL key");
-    if (!strcmp(key, "rs_variant")) { g_ctx.opt_variant = value; return BH_OK; }
     if (!strcmp(key, "blocks_per_cu")) {
         if (value < 0 || value > kMaxBlocksPerCu) return fail(BH_ERR_INVALID_ARG, "blocks_per_cu must be 0 (default) .. 8");
         g_ctx.opt_blocks_per_cu = value;
         return BH_OK;
     }
     if (!strcmp(key, "pcg_batch")) { g_ctx.opt_batch = std::max<int64_t>(0, value); return BH_OK; }
-    if (!strcmp(key, "pingpong")) { g_ctx.opt_pingpong = value ? 1 : 0; return BH_OK; }
-    if (!strcmp(key, "gram_nt")) { g_ctx.opt_gram_nt = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "proj_form")) { g_ctx.opt_proj_form = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "fold_init")) { g_ctx.opt_fold_init = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "cg_fused")) {
@@ -1474,7 +1404,6 @@ int32_t bh_set_option(const char* key, int64_t value) {
         return BH_OK;
     }
     if (!strcmp(key, "final_sync")) { g_ctx.opt_final_sync = value ? 1 : 0; return BH_OK; }
-    if (!strcmp(key, "mailbox_flush")) { g_ctx.opt_mbox_flush = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "host_copy_kernels")) { g_ctx.opt_host_copy_kernels = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "ls_from_cg")) { g_ctx.opt_ls_from_cg = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "step_from_cg")) { g_ctx.opt_step_from_cg = value ? 1 : 0; return BH_OK; }
@@ -1483,11 +1412,9 @@ int32_t bh_set_option(const char* key, int64_t value) {
     if (!strcmp(key, "cauchy_image")) { g_ctx.opt_cauchy_image = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "cauchy_gram")) { g_ctx.opt_cauchy_gram = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "cauchy_fused")) { g_ctx.opt_cauchy_fused = value ? 1 : 0; return BH_OK; }
-    if (!strcmp(key, "cauchy_fused_grid")) { g_ctx.opt_cauchy_fused_grid = std::min<int64_t>(std::max<int64_t>(0, value), kCauchyFusedGrid); return BH_OK; }
     if (!strcmp(key, "linv_refine")) { g_ctx.opt_linv_refine = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "cauchy_gemm")) { g_ctx.opt_cauchy_gemm = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "cauchy_image_max_ma")) { g_ctx.opt_cauchy_image_max_ma = std::min<int64_t>(std::max<int64_t>(0, value), 64); return BH_OK; }
-    if (!strcmp(key, "chol_blocked")) { g_ctx.opt_chol_blocked = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "image_pool")) {
         if (value < 0 || value > 8) return fail(BH_ERR_INVALID_ARG, "image_pool must be 0..8");
         g_ctx.opt_image_pool = value;
@@ -2331,7 +2258,7 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
     const bool rccl_gen = comm_active() && !use_peer_path() && fuse_gen;
     // Gram form: the fused and CGP shapes read J in their H*p launch — only the separate-kernel shape below goes through G
     const bool gram = H->form == BH_HESS_GRAM;
-    if (!gram && (box || fuse_gen) && g_ctx.opt_cg_fused && rs_cfg >= 0 && cgp_supported(rs_cfg) && (!comm_active() || peer_fused || rccl_gen) && max_iter >= 1 &&
+    if (!gram && (box || fuse_gen) && g_ctx.opt_cg_fused && rs_cfg >= 0 && (!comm_active() || peer_fused || rccl_gen) && max_iter >= 1 &&
         (gp == c.g || n == n_pad)) {
         BH_TRY(hess_ready(H));
         H->stats.cg_kernels = (box ? 2 : (gen_linv ? 3 : 4)) + (rccl_gen ? 1 : 0);
@@ -2581,11 +2508,11 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
     auto launch_iteration = [&](int index) -> int32_t {
         if (fold_init && index == 0) {
             // the state still holds the previous call's `done`: this launch is never a no-op, so it is not gated
-            BH_TRY(launch_hmul(H, gp, c.Hp, nullptr, index, 0, true, a.fixrank));                 // :722 with p = -P(g)
+            BH_TRY(launch_hmul(H, gp, c.Hp, nullptr, index, true, a.fixrank));                    // :722 with p = -P(g)
             launch_cg_first_step(a, s);
             return BH_OK;
         }
-        BH_TRY(launch_hmul(H, c.p, c.Hp, c.d_state, index, g_ctx.opt_pingpong ? (index & 1) : 0));   // :722
+        BH_TRY(launch_hmul(H, c.p, c.Hp, c.d_state, index));   // :722
         if (box) {
             launch_cg_step<0>(a, s);
         } else {
@@ -3198,8 +3125,8 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     const bool fused = image && !image_gen && !comm_active() && g_ctx.opt_cauchy_fused != 0;
     const int64_t img_rows = H->d + H->q_eff;
     const int img_grid = (int)std::max<int64_t>(1, std::min<int64_t>(fused ? kCauchyFusedGrid : kCauchyImgGrid, (img_rows + 255) / 256));
-    const int fused_grid = g_ctx.opt_cauchy_fused_grid > 0 ? (int)g_ctx.opt_cauchy_fused_grid
-                                                           : (int)std::max<int64_t>(1, std::min<int64_t>(kCauchyFusedGrid, (img_rows + CA_T - 1) / CA_T));
+    // (fewer, fatter workgroups measured slower: docs/design_history_r3.md)
+    const int fused_grid = (int)std::max<int64_t>(1, std::min<int64_t>(kCauchyFusedGrid, (img_rows + CA_T - 1) / CA_T));
     // with equalities a workgroup takes tiles of 64 rows; the partial sums still have to fit the [2][kCauchyImgGrid] slot
     const int gen_grid = (int)std::max<int64_t>(1, std::min<int64_t>(kCauchyImgGrid, (img_rows + 63) / 64));
     const bool gen_tiled = mA > 16;                                   // (few equalities: one row per thread, see bh_cauchy.hip.h)
@@ -3490,7 +3417,7 @@ int32_t bh_time_kernel(bh_hess* H, int32_t kind, int32_t reps, double* avg_ms) {
     BH_HIP(hipEventCreate(&evp.b));
     const hipEvent_t e0 = evp.a, e1 = evp.b;
     if (kind >= 9) {
-        // 9: a build of G (every launch a real build: gram_builds counts them); 10: one G·v launch (option "gram_nt" picks the loads)
+        // 9: a build of G (every launch a real build: gram_builds counts them); 10: one G·v launch
         BH_TRY(ensure_gram(H));
         auto one = [&]() -> int32_t {
             if (kind == 9) return launch_gram_build(H);

@@ -66,7 +66,6 @@ struct RowStreamArgs {
     double* sq_partials;    // gridDim.x or NULL (JV: sum_i weight_i * t_i^2, for vthv)
     double mu;
     const CgState* state;   // NULL, or skip the launch when state->done
-    int reverse;            // sweep the row groups last-to-first (ping-pong order keeps the tail of J in the Infinity Cache)
     int accumulate;         // JV: t_out += (column panels of a wide J are swept one launch each)
     int weighted_u;         // JTV: coefficient u[row] * (row < d_rows ? 1 : mu)  (second pass of the two-pass H*p)
     int negate;             // JV/FUSED: use -mask(v) instead of v (first CG iteration: p0 = -P(g) for box constraints, :706-708)
@@ -74,9 +73,10 @@ struct RowStreamArgs {
     CgFuse cf;              // CGP = 1 only
 };
 
-// NT: J is read exactly once per launch -> non-temporal loads (global_load_dwordx4 ... nt): measured +10 % (6.39 -> 7.05 TB/s).
-// PF: 1 = issue the next row group's loads before reducing the current one (two register buffers); 0 = one buffer, latency
-// hidden by several co-resident workgroups instead.
+// NT, PF: always 1 (the parameters stay so that the symbol names do not change).  NT: J is read exactly once per launch ->
+// non-temporal loads (global_load_dwordx4 ... nt): measured +10 % (6.39 -> 7.05 TB/s) over plain loads.  PF: the next row group's
+// loads are issued before the current one is reduced (two register buffers); one buffer with several co-resident workgroups
+// hiding the latency measured slower.
 // VL: 1 = each lane parks its slice of v in LDS (dynamic, nchunks x 16 bytes, lane-private slots: no barrier, no bank
 // conflicts) instead of registers.  For 8192 < n <= 16384 the two row buffers and the z accumulators of the fused mode
 // fill the register file on their own; the 128 KiB of LDS a CU has left over hold v.
@@ -87,6 +87,7 @@ struct RowStreamArgs {
 // rocprofv3 --stats summary.  Either symbol does the right thing if the prediction is wrong.
 template <int T, int CPT, int R, int MODE, int NT = 1, int PF = 1, int VL = 0, int CGP = 0>
 __global__ __launch_bounds__(T) void row_stream_kernel(RowStreamArgs a) {
+    static_assert(NT == 1 && PF == 1, "plain loads (NT = 0) and the single register buffer (PF = 0) lost their A/Bs and were removed");
     if (!CGP && a.state != nullptr && a.state->done) return;
     // the loop stopped before this iteration (CGP = 3: the launch that FINDS the stop is j = stop_at + 1 and writes stop_at itself —
     // every one of its workgroups must still get through its prologue, whose owner stores complete w)
@@ -112,7 +113,6 @@ __global__ __launch_bounds__(T) void row_stream_kernel(RowStreamArgs a) {
     int buf = 0;
 
     auto load_group = [&](double2 (&dst)[R][CPT], int64_t grp) {
-        if (a.reverse) grp = ngroups - 1 - grp;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int64_t row = grp * R + r;
@@ -122,19 +122,14 @@ __global__ __launch_bounds__(T) void row_stream_kernel(RowStreamArgs a) {
             for (int k = 0; k < CPT; ++k) {
                 dst[r][k] = make_double2(0.0, 0.0);
                 if (rv && act[k]) {
-                    if (NT) {
-                        const dvec2 t = __builtin_nontemporal_load(reinterpret_cast<const dvec2*>(rp + tid + k * T));
-                        dst[r][k] = make_double2(t.x, t.y);
-                    } else {
-                        dst[r][k] = rp[tid + k * T];
-                    }
+                    const dvec2 t = __builtin_nontemporal_load(reinterpret_cast<const dvec2*>(rp + tid + k * T));
+                    dst[r][k] = make_double2(t.x, t.y);
                 }
             }
         }
     };
 
     auto process = [&](double2 (&X)[R][CPT], int64_t grp) {
-        if (a.reverse) grp = ngroups - 1 - grp;
         double s[R];
         if (MODE != MODE_JTV) {
 #pragma unroll
@@ -206,7 +201,7 @@ __global__ __launch_bounds__(T) void row_stream_kernel(RowStreamArgs a) {
     }
     if (!CGP || a.cf.j == 1) {
         // the first row group does not depend on the vector: its loads go out first
-        if (PF && g < ngroups) load_group(A, g);
+        if (g < ngroups) load_group(A, g);
         // (all loads first, the masking afterwards: a compare next to its load makes the compiler wait for each chunk in turn)
         int2 nm[CPT];
 #pragma unroll
@@ -374,7 +369,7 @@ __global__ __launch_bounds__(T) void row_stream_kernel(RowStreamArgs a) {
                 publish_word(f.mirror, f.tag, status, stop ? 1 : 0, cont ? f.j : it, it, tr);
             }
             if (stop) return;
-            if (PF && g < ngroups) load_group(A, g);                           // the stream starts here (no prefetch before the exit test)
+            if (g < ngroups) load_group(A, g);                                 // the stream starts here (no prefetch before the exit test)
 #pragma unroll
             for (int k = 0; k < CPT; ++k) {
                 vv[k].x = __dadd_rn(-vk[k].x, __dmul_rn(beta, po[k].x));       // :745
@@ -443,7 +438,7 @@ __global__ __launch_bounds__(T) void row_stream_kernel(RowStreamArgs a) {
             // operands (v, p, the r.v partials: L2 hits) arrive right behind it and the prologue's arithmetic runs while nothing
             // else is outstanding; issued the other way round the stream would start one memory round trip later.  If the loop
             // turns out to have stopped, the 128 KiB this workgroup asked for are simply dropped.
-            if (CGP != 2 && PF && g < ngroups) load_group(A, g);
+            if (CGP != 2 && g < ngroups) load_group(A, g);
             double2 vk[CPT], po[CPT];
 #pragma unroll
             for (int k = 0; k < CPT; ++k) {
@@ -478,7 +473,7 @@ __global__ __launch_bounds__(T) void row_stream_kernel(RowStreamArgs a) {
                 publish_word(f.mirror, f.tag, status, stop ? 1 : 0, f.j, f.j - 1, tr);
             }
             if (stop) return;
-            if (CGP == 2 && PF && g < ngroups) load_group(A, g);              // the prediction was wrong: carry on
+            if (CGP == 2 && g < ngroups) load_group(A, g);                    // the prediction was wrong: carry on
 #pragma unroll
             for (int k = 0; k < CPT; ++k) {
                 vv[k].x = __dadd_rn(-vk[k].x, __dmul_rn(beta, po[k].x));       // :745
@@ -517,12 +512,7 @@ __global__ __launch_bounds__(T) void row_stream_kernel(RowStreamArgs a) {
         for (int k = 0; k < CPT; ++k) v_lds[k * T + tid] = vv[k];     // read back only by this lane
     }
 
-    if (!PF) {
-        for (; g < ngroups; g += G) {
-            load_group(A, g);
-            process(A, g);
-        }
-    } else if (g < ngroups) {
+    if (g < ngroups) {
         while (true) {
             int64_t gn = g + G;
             if (gn < ngroups) load_group(B, gn);

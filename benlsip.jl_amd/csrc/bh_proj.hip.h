@@ -291,46 +291,6 @@ __global__ __launch_bounds__(GRAM_T) void gram_free_mfma_kernel(const double* __
     }
 }
 
-// In-place lower Cholesky of the mA x mA matrix M (column-major, lower triangle), single workgroup, right-looking.
-// info[0] = 0 on success, else 1 + index of the first non-positive pivot (the reference's PosDefException).
-__global__ __launch_bounds__(CG_T) void chol_lower_kernel(const double* __restrict__ Msrc, double* __restrict__ M, int m, int* info,
-                                                          const CgState* gate) {
-    if (gate != nullptr && gate->done) return;
-    __shared__ double s_piv;
-    const int tid = threadIdx.x;
-    if (tid == 0) info[0] = 0;
-    for (int64_t e = tid; e < (int64_t)m * m; e += CG_T) M[e] = Msrc[e];
-    __syncthreads();
-    for (int j = 0; j < m; ++j) {
-        if (tid == 0) {
-            const double d = M[j + (int64_t)j * m];
-            if (!(d > 0.0) && info[0] == 0) info[0] = j + 1;
-            s_piv = sqrt(d);
-        }
-        __syncthreads();
-        const double piv = s_piv;
-        for (int i = j + tid; i < m; i += CG_T) M[i + (int64_t)j * m] = (i == j) ? piv : M[i + (int64_t)j * m] / piv;
-        __syncthreads();
-        // trailing update of the lower triangle: M[i][k] -= L[i][j]*L[k][j], j < k <= i.  32 x 32 thread tiles over the
-        // lower triangle (tx along i: coalesced in the column-major matrix; no integer division per element).
-        const int rem = m - j - 1;
-        const int tx = tid & 31, ty = tid >> 5;
-        const double* colj = M + (int64_t)j * m + (j + 1);
-        for (int kb = 0; kb < rem; kb += 32) {
-            const int kk = kb + ty;
-            const double lkj = (kk < rem) ? colj[kk] : 0.0;
-            for (int ib = kb; ib < rem; ib += 32) {
-                const int ii = ib + tx;
-                if (ii < rem && kk < rem && ii >= kk) {
-                    double* e = M + (int64_t)(j + 1 + kk) * m + (j + 1 + ii);
-                    *e = fma(-colj[ii], lkj, *e);
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
 // Reduced-form factor for mA <= 64: right-looking Cholesky on 256 threads.  lane = row, wave w owns the 16-column panel
 // [16w, 16w+16) of that row in REGISTERS (statically indexed: the column loop is unrolled per panel); each step the
 // owning wave publishes column j through a double-buffered 64-entry LDS vector (one barrier per step) and every wave

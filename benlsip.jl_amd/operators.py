@@ -189,7 +189,7 @@ class AlHessian:
     def time_kernel(self, kind, reps=20):
         """Average hipEvent milliseconds of one launch: kind 0 = fused J'(Jp), 1 = J v, 2 = J'u, 3..6 = read-only stream probe with 1/2/4/8 workgroups per CU,
         7 = all-reduce of one n-vector, 8 = slab reduction (+ exchange) of an H*p; Gram form only (``set_form("gram")``): 9 = a build of G,
-        10 = one G·v launch (option "gram_nt" selects non-temporal loads)."""
+        10 = one G·v launch."""
         ms = ct.c_double(0.0)
         check(_lib.lib().bh_time_kernel(self._h, kind, reps, ct.byref(ms)), "bh_time_kernel")
         return ms.value

@@ -328,7 +328,8 @@ int32_t bh_dev_upload(void* dst_dev, const void* src_host, int64_t bytes);
 int32_t bh_dev_download(void* dst_host, const void* src_dev, int64_t bytes);
 int32_t bh_stats(bh_hess* H, bh_stats_t* out);
 int32_t bh_stats_reset(bh_hess* H);
-/* Tuning knobs; unknown keys return BH_ERR_INVALID_ARG.  Defaults in brackets.
+/* Tuning knobs; unknown keys return BH_ERR_INVALID_ARG.  Defaults in brackets.  (A key whose A/B experiment is decided leaves
+ * this list together with the losing path, and is an unknown key from then on.)
  *   "proj_form"      [1] 1 = reduced mA x mA projection (factor built on the device), 0 = the reference's augmented form
  *                        (needs the caller's factor in bh_proj_set_active)
  *   "pcg_batch"      [0] CG iterations enqueued per launch-ahead batch; 0 = by problem size (1 when an H*p streams >= 100 us)
@@ -360,8 +361,6 @@ int32_t bh_stats_reset(bh_hess* H);
  *                        copy kernel on the mapped arena instead of a DMA engine transfer, and the call ends with a mailbox seal +
  *                        poll instead of hipStreamSynchronize (bh_pcg 0.660 -> 0.652 ms, bh_minor_iterate 0.693 -> 0.665 ms,
  *                        bh_project 31 -> 21 us on the config-3 instance); 0 = DMA + synchronize (round 1)
- *   "mailbox_flush"  [0] experiment: end the host-pointer entry points with a mailbox seal + poll instead of
- *                        hipStreamSynchronize (measured slower behind a D2H DMA; docs/design_history_r1_r2.md §4)
  *   "ls_from_cg"     [1] bh_minor_iterate: w'Hw of the line search from the H*w the CG loop accumulated (0: explicit vthv)
  *   "step_from_cg"   [0] opt-in (the resident inner-step mirrors set it around their loop): bh_step_accumulate_dev called right
  *                        behind the bh_minor_iterate_dev that produced its w (same handle,
@@ -388,20 +387,14 @@ int32_t bh_stats_reset(bh_hess* H);
  *                        search in ONE launch from G (init -> G d -> cauchy_gram_kernel: Hd downdated by one row of G per breakpoint, the
  *                        loop runs on the device; the launch count does not depend on the number of breakpoints).  Any other handle or
  *                        constraint set takes the path it takes with 0.  bh_cauchy_info tells which form ran
- *   "cauchy_fused_grid" [0] workgroups of that kernel (0: one row per thread up to 256 workgroups; measured best — tools/scratch/cauchy_grid_sweep.py)
  *   "linv_refine"    [1] three-kernel CG iteration with linear equalities (cg_fused = 1): one step of iterative refinement behind the
  *                        explicit inverse of the factor (rho = t - A_free A_free' y, y += L^-T L^-1 rho), so that A_free v stays at the level
  *                        of the reference's two triangular solves also for ill-conditioned A_free A_free' (0: plain explicit inverse;
  *                        not applied with a single equality, where the factor is a scalar)
  *   "cauchy_gemm"    [1] B = J D A' in ONE sweep over J on the fp64 matrix cores (a tall-skinny GEMM: M = rows of J, N = mA, K = n);
  *                        0: mA J v sweeps over the masked rows of A
- *   "chol_blocked"   [1] mA > 64: blocked potrf / trsm / syrk (0: one-workgroup kernel)
  *   "gram_mfma"      [1] A_free A_free' on fp64 MFMA when mA > 96 (2: always, 0: never)
- *   "rs_variant"     [0] A/B geometries of the row-streaming kernel for 2048 < n <= 4096 (tools/kernel_ab.py)
  *   "blocks_per_cu"  [0] workgroups per CU of the row-streaming kernels (0: per-geometry default)
- *   "pingpong"       [0] alternate the sweep direction of J between consecutive H*p
- *   "gram_nt"        [1] Gram form (bh_hess_set_form): G·v with non-temporal loads (1) or plain loads (0).  Although every product
- *                        re-reads G, the non-temporal loads measured faster at every size (config 3: 21.9 against 22.4 us per launch)
  *   "blocks_per_cu" accepts 0..8 (the partial-slab buffers hold 8 workgroups per CU); anything else is BH_ERR_INVALID_ARG
  *   "comm_path"      [0 with BH_COMM=rccl|both, 1 with BH_COMM=ipc] which communicator carries the all-reduces: 0 = RCCL,
  *                        1 = the one-shot peer-buffer exchange fused into the slab reduction (needs BH_COMM=ipc or both)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The explicit Gram form of the Gauss-Newton Hessian (bh_hess_set_form) against the implicit one, on synthetic instances:
-build of G (ms, TFLOP/s of the useful lower-triangle flop 2 (d+q) n (n+1)/2), one G·v launch with and without non-temporal
-loads (us, GB/s of its 8 n ld bytes), us per CG iteration of projected_cg (bench instance, "ic" columns: long runs) in both
+build of G (ms, TFLOP/s of the useful lower-triangle flop 2 (d+q) n (n+1)/2), one G·v launch
+(us, GB/s of its 8 n ld bytes), us per CG iteration of projected_cg (bench instance, "ic" columns: long runs) in both
 forms, whole projected_cg on the "ic" variant, us per breakpoint of an H*d Cauchy search with mA = 96, and the break-even
 number of products per J.  (Not to be confused with tools/gram_timing.py, which times A_free A_free'.)
 
@@ -65,17 +65,12 @@ def main():
         H.set_form("gram")
         ms_build = H.time_kernel(9, reps=3)
         flop = 2.0 * d * n * (n + 1) / 2
-        gv = {}
-        for nt in (0, 1):
-            bh.set_option("gram_nt", nt)
-            gv[nt] = 1e3 * H.time_kernel(10, reps=50)
-        bh.set_option("gram_nt", 1)                       # the default
+        gv = 1e3 * H.time_kernel(10, reps=50)
         us_gram, st_gram, it_gram, nh_gram = pcg_us(H, cons, dv, 3)
         per_imp, per_gram = us_imp / max(nh_imp, 1), us_gram / max(nh_gram, 1)
-        say("%s (d = %d, n = %d, ic): build of G %.3f ms = %.1f TFLOP/s (useful lower-triangle flop %.3g); G·v %.1f us = %.0f GB/s plain, "
-            "%.1f us = %.0f GB/s non-temporal; implicit fused H*p %.1f us"
-            % (label, d, n, ms_build, flop / (ms_build * 1e-3) / 1e12, flop, gv[0], 8.0 * n * ld / (gv[0] * 1e-6) / 1e9, gv[1],
-               8.0 * n * ld / (gv[1] * 1e-6) / 1e9, t_imp_hmul))
+        say("%s (d = %d, n = %d, ic): build of G %.3f ms = %.1f TFLOP/s (useful lower-triangle flop %.3g); G·v %.1f us = %.0f GB/s; "
+            "implicit fused H*p %.1f us"
+            % (label, d, n, ms_build, flop / (ms_build * 1e-3) / 1e12, flop, gv, 8.0 * n * ld / (gv * 1e-6) / 1e9, t_imp_hmul))
         say("    projected_cg (bh_pcg_dev): implicit %.1f us, status %d, %d iterations, %d H*p = %.1f us per H*p; Gram %.1f us, status %d, "
             "%d iterations, %d H*p = %.1f us per H*p  (%.2fx per iteration)"
             % (us_imp, st_imp, it_imp, nh_imp, per_imp, us_gram, st_gram, it_gram, nh_gram, per_gram, per_imp / per_gram))
