@@ -1191,10 +1191,11 @@ def test_cauchy_step_on_the_pinned_multimodal_operands(bh, capsys, image):
 
 
 # ----------------------------------------------------------------------------- wide J (n > 8192)
-@pytest.mark.parametrize("d,n,q", [(70, 8200, 1), (40, 10001, 0), (29, 16384, 1), (31, 16385, 0), (33, 20000, 2)])
+@pytest.mark.parametrize("d,n,q", [(70, 8200, 1), (40, 10001, 0), (29, 16384, 1), (31, 16385, 0), (33, 20000, 2), (1100, 16400, 2)])
 def test_wide_jacobian_column_panels(bh, d, n, q):
     """8192 < n <= 16384: one row per step, the fused kernel parks its slice of v in LDS (still a single read of J);
-    n > 16384: J is swept in 4096-column panels (two-pass H*p).  CG runs on the generic n-vector kernels in both."""
+    n > 16384: J is swept in 4096-column panels (two-pass H*p).  CG runs on the generic n-vector kernels in both.
+    The last shape has more row groups (276) than the panel sweeps have workgroups (256): their stream turns over."""
     rng = np.random.default_rng(n)
     J, C, mu = rng.standard_normal((d, n)), rng.standard_normal((q, n)), 0.5
     v, u = rng.standard_normal(n), rng.standard_normal(d)
