@@ -117,6 +117,7 @@ struct Ctx {
     int64_t opt_cauchy_gram = 0;            // Gram-form handle, box constraints, one rank: the whole search from G in one launch (cauchy_gram_kernel)
     int64_t opt_linv_refine = 1;            // explicit-inverse projection (three-kernel CG iteration): one step of iterative refinement of y
     int64_t opt_cauchy_gemm = 1;            // B = J D A' of that form in one sweep on the matrix cores (0: mA J v sweeps over masked rows of A)
+    int64_t opt_gram_cg_fused = 0;          // Gram-form handle: fused CG iteration (gram_cg_kernel + update: two kernels; <= 64 equalities: three)
     int64_t opt_gram_mfma = 1;       // A_free A_free': 1 = matrix cores when mA > 96, 2 = always, 0 = never (one wave per entry, VALU)
     int64_t opt_ls_from_cg = 1;      // minor_iterate: linesearch's w'Hw from the H*w accumulated by the CG loop
     // bh_step_accumulate_dev right behind the bh_minor_iterate_dev that produced its w: g_minor += H*w with the H*w that CG loop
@@ -332,6 +333,26 @@ void launch_row_stream_cgp(int cfg, const RowStreamArgs& a, int grid, hipStream_
             else hipLaunchKernelGGL((row_stream_kernel<512, 16, 1, MODE_FUSED, 1, 1, 1, 1>), dim3(grid), dim3(512), lds, s, a);
             break;
         }
+    }
+}
+
+// Gram form, option gram_cg_fused: G·v with the CG prologue (bh_gramcg.hip.h), the geometries of kRsConfigs over the ld rows of G.
+// Every instantiation holds its slice of p and both row buffers in registers (no z accumulators: nothing is parked in LDS).
+template <int T, int CPT, int R>
+void launch_gram_cg_geom(const RowStreamArgs& a, int grid, hipStream_t s, bool expect_stop) {
+    if (expect_stop) hipLaunchKernelGGL((gram_cg_kernel<T, CPT, R, 1>), dim3(grid), dim3(T), 0, s, a);
+    else hipLaunchKernelGGL((gram_cg_kernel<T, CPT, R, 0>), dim3(grid), dim3(T), 0, s, a);
+}
+
+void launch_gram_cg(int cfg, const RowStreamArgs& a, int grid, hipStream_t s, bool expect_stop) {
+    switch (cfg) {
+        case 0: launch_gram_cg_geom<64, 1, 8>(a, grid, s, expect_stop); break;
+        case 1: launch_gram_cg_geom<256, 1, 8>(a, grid, s, expect_stop); break;
+        case 2: launch_gram_cg_geom<256, 2, 8>(a, grid, s, expect_stop); break;
+        case 3: launch_gram_cg_geom<256, 4, 4>(a, grid, s, expect_stop); break;
+        case 4: launch_gram_cg_geom<256, 8, 4>(a, grid, s, expect_stop); break;
+        case 5: launch_gram_cg_geom<512, 8, 2>(a, grid, s, expect_stop); break;
+        default: launch_gram_cg_geom<512, 16, 1>(a, grid, s, expect_stop); break;
     }
 }
 
@@ -1411,6 +1432,13 @@ int32_t bh_set_option(const char* key, int64_t value) {
     if (!strcmp(key, "chol_downdate")) { g_ctx.opt_chol_downdate = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "cauchy_image")) { g_ctx.opt_cauchy_image = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "cauchy_gram")) { g_ctx.opt_cauchy_gram = value ? 1 : 0; return BH_OK; }
+    if (!strcmp(key, "gram_cg_fused")) {
+        // selects a device path of the product: like every product-path call it needs bh_init (switching it off never fails)
+        if (value != 0) BH_REQUIRE_INIT();
+        if (value != 0 && value != 1) return fail(BH_ERR_INVALID_ARG, "gram_cg_fused is 0 or 1");
+        g_ctx.opt_gram_cg_fused = value;
+        return BH_OK;
+    }
     if (!strcmp(key, "cauchy_fused")) { g_ctx.opt_cauchy_fused = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "linv_refine")) { g_ctx.opt_linv_refine = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "cauchy_gemm")) { g_ctx.opt_cauchy_gemm = value ? 1 : 0; return BH_OK; }
@@ -2244,8 +2272,15 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
     // single-workgroup 128-step triangular solve) before forming its chunks of v = P(r) and its partial of r.v.
     // cg_fused = 2: FOUR kernels — the triangular solves in a launch of their own (trsv_small_kernel summing the partials),
     // then left_mul_tr.  Both change pHp's rounding like the box form does (cg_fused = 0 keeps dot(p, H*p)).
-    const bool fuse_gen = !box && g_ctx.opt_cg_fused >= 1 && P->reduced && P->mA <= 64 && P->tpart != nullptr && P->ldA == H->ld;
-    const bool gen_linv = fuse_gen && g_ctx.opt_cg_fused == 1 && P->W != nullptr;
+    // Gram form: the fused shapes are opt-in through an option of their own (gram_cg_fused, independent of cg_fused; a Gram handle is
+    // single-rank by construction) and exist in the two- and the three-kernel form only — gram_cg_kernel streams G instead of J
+    // and leaves H*p as one finished vector with the partials of dot(p, H*p) (bh_gramcg.hip.h); everything else takes the
+    // separate-kernel shape below, as every Gram handle does without the option.
+    const bool gram = H->form == BH_HESS_GRAM;
+    const int64_t cg_fused = !gram ? g_ctx.opt_cg_fused : (g_ctx.opt_gram_cg_fused != 0 && !comm_active()) ? 1 : 0;
+    const bool fuse_gen = !box && cg_fused >= 1 && P->reduced && P->mA <= 64 && P->tpart != nullptr && P->ldA == H->ld &&
+                          (!gram || P->W != nullptr);
+    const bool gen_linv = fuse_gen && cg_fused == 1 && P->W != nullptr;
     // (one equality: the "factor" is a scalar, y = t / l^2 has no conditioning to repair — the refinement step would only move the last bit)
     const bool linv_refine = gen_linv && g_ctx.opt_linv_refine != 0 && P->M_valid && P->mA >= 2;
     // Several ranks: the two-kernel (equalities: three-kernel) form carries the exchange inside the update kernel when the
@@ -2256,14 +2291,13 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
     // p'Hp behind the vector, as in the box form below) and the update kernel, which then sums ONE slab — the all-reduced H*p:
     //   S(1) | R(1) AR(1) U(1) P(1) S(2) | ...   four kernels + the collective instead of seven, on the lock-step launch schedule.
     const bool rccl_gen = comm_active() && !use_peer_path() && fuse_gen;
-    // Gram form: the fused and CGP shapes read J in their H*p launch — only the separate-kernel shape below goes through G
-    const bool gram = H->form == BH_HESS_GRAM;
-    if (!gram && (box || fuse_gen) && g_ctx.opt_cg_fused && rs_cfg >= 0 && (!comm_active() || peer_fused || rccl_gen) && max_iter >= 1 &&
+    if ((box || fuse_gen) && cg_fused && rs_cfg >= 0 && (!comm_active() || peer_fused || rccl_gen) && max_iter >= 1 &&
         (gp == c.g || n == n_pad)) {
         BH_TRY(hess_ready(H));
+        if (gram) BH_TRY(ensure_gram(H));                  // G rebuilt first when stale, on the same stream
         H->stats.cg_kernels = (box ? 2 : (gen_linv ? 3 : 4)) + (rccl_gen ? 1 : 0);
         if (gp == c.g && n < n_pad && !g_pad_zeroed) BH_HIP(hipMemsetAsync(c.g + n, 0, (size_t)(n_pad - n) * sizeof(double), s));
-        const int64_t nrows = H->d + H->q_eff;
+        const int64_t nrows = gram ? H->ld : H->d + H->q_eff;    // Gram form: the rows of the ld x ld image of G
         const int grid = grid_for(rs_cfg, nrows);
         const int nblk = (H->nchunks + 15) / 16;
         double* pbuf[2] = {c.p, c.p2};
@@ -2293,6 +2327,7 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
         auto launch_stream = [&](int j) -> int32_t {            // H*p of iteration j (1-based), p_j formed on the fly
             RowStreamArgs ra = rs_args(H, nrows, nullptr);
             ra.partials = H->partials;
+            if (gram) { ra.J = H->G; ra.d_rows = nrows; ra.mu = 1.0; ra.partials = nullptr; ra.t_out = c.Hp; }     // H*p leaves as one vector
             if (fuse_gen) { ra.v = c.p; ra.negate = 0; }                            // used by j == 1 only: p_1 = -P(g), formed by the init kernels
             else { ra.v = gp; ra.negate = 1; ra.negmask = a.fixrank; }             //                      p_1 = -mask(g), formed on the fly
             CgFuse& f = ra.cf;
@@ -2308,7 +2343,8 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
             BH_TRY(profile_begin(H, j - 1, &slot));
             // a handle without history cannot predict its exit: its look-ahead launches (j > 1) take the no-prefetch symbol too, so
             // that launches which stop in their prologue never show up under the streaming kernel's name in a profile
-            launch_row_stream_cgp(rs_cfg, ra, grid, s, expect_stop);
+            if (gram) launch_gram_cg(rs_cfg, ra, grid, s, expect_stop);
+            else launch_row_stream_cgp(rs_cfg, ra, grid, s, expect_stop);
             if (slot >= 0) BH_HIP(hipEventRecord(H->ev[2 * slot + 1], s));
             return BH_OK;
         };
@@ -2318,6 +2354,9 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
             u.sqpart = H->sq_partials; u.gpart = H->sq_partials + H->g_cap; u.rvpart_in = rvbuf[(j - 1) & 1]; u.rvpart_out = rvbuf[j & 1]; u.nrv = nrv;
             u.p = pbuf[j & 1]; u.w = wp; u.hw = hw; u.r = c.r; u.g = gp; u.v = c.v; u.fixrank = a.fixrank;
             u.n = (int)n; u.atol_neg = atol_negcurv; u.trace = a.trace; u.trace_cap = a.trace_cap; u.mirror = a.mirror; u.tag = a.tag;
+            // Gram form: ONE "slab", the finished G p; the partials of dot(p, H*p) and of gamma stay one per workgroup of the G·v grid
+            // (up to n_cu * kMaxBlocksPerCu of them: LaneBatch holds the first 512 in registers and folds the rest in index order)
+            if (gram) { u.partials = c.Hp; u.Gs = 1; }
             if (!fuse_gen) {
                 if (peer_fused) hipLaunchKernelGGL((cg_reduce_update_kernel<false, true>), dim3(nblk), dim3(256), 0, s, u, g_ctx.peer.args);
                 else hipLaunchKernelGGL((cg_reduce_update_kernel<false, false>), dim3(nblk), dim3(256), 0, s, u, PeerArgs{});

@@ -26,3 +26,4 @@
 #include "bh_cauchygram.hip.h"
 #include "bh_minor.hip.h"
 #include "bh_gngram.hip.h"
+#include "bh_gramcg.hip.h"

@@ -485,6 +485,9 @@ def resid_sqnorm(rx):
 
 
 def set_option(key, value):
+    """``bh_set_option``: process-wide integer options (the list with defaults is in include/benlsip_hip.h), e.g. ``cg_fused``,
+    ``proj_form``, ``cauchy_image``, ``cauchy_gram`` and ``gram_cg_fused`` (fused two- / three-kernel CG iteration on a
+    Gram-form handle, default 0)."""
     check(_lib.lib().bh_set_option(key.encode(), int(value)), "bh_set_option(%s)" % key)
 
 

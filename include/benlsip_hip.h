@@ -82,7 +82,9 @@ typedef struct bh_stats_t {
     /* launch shape of the last bh_pcg on this handle: kernels per CG iteration in the fused forms, the collective not counted
      * (box constraints 2, on one rank and over either transport; equalities 3 through the explicit factor inverse — 4 with
      * cg_fused = 2 — on one rank and over the peer buffers, one more over RCCL: the slab reduction in front of ncclAllReduce);
-     * 0 = the separate-kernel forms (three kernels for box constraints, seven with equalities; option "cg_fused"). */
+     * 0 = the separate-kernel forms (three kernels for box constraints, seven with equalities; option "cg_fused").
+     * On a handle in the Gram form: 0 (G·v + single-workgroup step kernel; six launches with equalities) unless option
+     * "gram_cg_fused" is on, then 2 (box constraints) or 3 (up to 64 equalities in the reduced projection form), 0 otherwise. */
     int64_t cg_kernels;
 } bh_stats_t;
 
@@ -161,8 +163,9 @@ int32_t bh_hess_destroy(bh_hess* H);
  *                     finished, on the library stream, without a host synchronisation — and every such product is ONE G·v launch
  *                     (8 n ld bytes instead of 8 (d+q) n; no slab reduction).  A new mu (bh_hess_set_mu) rebuilds it once.
  *   Reading G in the Gram form: Base.:*(H, v) — src/basic_tralcnlss.jl:102-106 (bh_hmul, bh_hmul_dev), bh_hmul_add(_dev) and
- *   bh_step_accumulate_dev, the H*p of projected_cg(...) — src/basic_tralcnlss.jl:690-764 (bh_pcg*, bh_minor_iterate*: always the
- *   separate-kernel CG shape, stats.cg_kernels = 0, pHp = dot(p, H*p) as the reference forms it at :723) and the H*d form of
+ *   bh_step_accumulate_dev, the H*p of projected_cg(...) — src/basic_tralcnlss.jl:690-764 (bh_pcg*, bh_minor_iterate*: by default the
+ *   separate-kernel CG shape, stats.cg_kernels = 0, pHp = dot(p, H*p) as the reference forms it at :723; with option
+ *   "gram_cg_fused" = 1 the fused shape, stats.cg_kernels = 2 or 3, the same dot(p, H*p) summed per workgroup) and the H*d form of
  *   cauchy_step(...) — src/basic_tralcnlss.jl:574-639 (cauchy_image = 0, or more linear equalities than its row-space form takes);
  *   with option "cauchy_gram" = 1 also the whole box-constrained search of cauchy_step(...) (no linear equalities, one rank):
  *   Hd = G d once, then one row of G per breakpoint inside ONE launch (cauchy_gram_kernel).
@@ -387,6 +390,13 @@ int32_t bh_stats_reset(bh_hess* H);
  *                        search in ONE launch from G (init -> G d -> cauchy_gram_kernel: Hd downdated by one row of G per breakpoint, the
  *                        loop runs on the device; the launch count does not depend on the number of breakpoints).  Any other handle or
  *                        constraint set takes the path it takes with 0.  bh_cauchy_info tells which form ran
+ *   "gram_cg_fused"  [0] bh_pcg*, bh_minor_iterate* on a handle in the Gram form (one rank by construction), independent of "cg_fused":
+ *                        TWO kernels per CG iteration with box constraints (gram_cg_kernel: G·v with p_j, beta and the exit test formed
+ *                        in its prologue, H*p stored as one vector next to per-workgroup partials of dot(p, H*p); then
+ *                        cg_reduce_update_kernel), THREE with up to 64 linear equalities in the reduced projection form (+
+ *                        proj_apply_linv_kernel).  Any other case (mA > 64, proj_form = 0, nothing free, g not readable to the padded
+ *                        length) and every call with 0 takes the separate-kernel shape.  stats.cg_kernels tells which shape ran.
+ *                        Switching it on needs bh_init (BH_ERR_NOT_INIT otherwise); values other than 0 / 1: BH_ERR_INVALID_ARG
  *   "linv_refine"    [1] three-kernel CG iteration with linear equalities (cg_fused = 1): one step of iterative refinement behind the
  *                        explicit inverse of the factor (rho = t - A_free A_free' y, y += L^-T L^-1 rho), so that A_free v stays at the level
  *                        of the reference's two triangular solves also for ill-conditioned A_free A_free' (0: plain explicit inverse;

@@ -6,6 +6,12 @@ forms, whole projected_cg on the "ic" variant, us per breakpoint of an H*d Cauch
 number of products per J.  (Not to be confused with tools/gram_timing.py, which times A_free A_free'.)
 
     python tools/gn_gram_timing.py [--out FILE] [--quick]
+    python tools/gn_gram_timing.py --cg-fused [--out FILE] [--one]
+
+--cg-fused: the CG iteration on a Gram-form handle with option gram_cg_fused 0 / 1 alternated in one process (same handle, same
+subproblem): median of 5 bh_pcg_dev calls each, wall time per call / H*p products, with the min - max spread; box constraints
+at config 2, config 3 and n = 8192, and config 3 with 64 ("config-5 shape") and 8 linear equalities (A = u(4, .)).
+--one: a single pair of calls on the config-5 shape with the option on, nothing else (rocprofv3 kernel traces).
 """
 import argparse
 import os
@@ -47,12 +53,65 @@ def instance(d, n, kind):
     return H, cons, dv, dict(x=x, x_l=x_l, x_u=x_u, g=g)
 
 
+def cg_fused_mode(args):
+    syn = bh.synthetic
+    shapes = [("config 2", 8192, 1024, [0]), ("config 3", 65536, 4096, [0, 64, 8]), ("n = 8192", 32768, 8192, [0])]
+    if args.one:
+        shapes = [("config 3", 65536, 4096, [64])]
+    say("# tools/gn_gram_timing.py --cg-fused: CG iteration on a Gram-form handle, option gram_cg_fused 0 / 1 alternated in one process, one "
+        "MI355X; wall time of bh_pcg_dev / H*p products, median of 5 calls (min - max); ic columns, kappa2 = 0.1")
+    for label, d, n, mas in shapes:
+        H, cons_box, dv, v = instance(d, n, 1)
+        H.set_form("gram")
+        _, _, _, fix = syn.box_vectors(n, fix_every=8)
+        for mA in mas:
+            cons = cons_box
+            if mA:
+                A = syn.splitmix_uniform(4, np.arange(mA * n)).reshape((mA, n), order="F")
+                cons = bh.MixedConstraints(A, None, fix, l=v["x_l"], u=v["x_u"])
+            run = lambda: bh.operators.projected_cg_dev(dv["g"], H, dv["wl"], dv["wu"], cons, 0.1, dv["w"])
+            times, seen = {0: [], 1: []}, {}
+            try:
+                for opt in ((1, 1) if args.one else (0, 1)):         # preheat: the build of G, both shapes once
+                    bh.set_option("gram_cg_fused", opt)
+                    run()
+                for _ in range(0 if args.one else 5):
+                    for opt in (0, 1):
+                        bh.set_option("gram_cg_fused", opt)
+                        t0 = time.perf_counter()
+                        st, it, nh = run()
+                        times[opt].append(1e6 * (time.perf_counter() - t0) / max(nh, 1))
+                        seen[opt] = (int(st), it, nh, H.stats()["cg_kernels"])
+            finally:
+                bh.set_option("gram_cg_fused", 0)
+            if args.one:
+                continue
+            med = {o: float(np.median(times[o])) for o in (0, 1)}
+            spread = max(max(times[o]) - min(times[o]) for o in (0, 1))
+            verdict = "faster" if med[0] - med[1] > spread else "slower" if med[1] - med[0] > spread else "no difference beyond the spread"
+            say("%s (d = %d, n = %d, mA = %d): option 0: status %d, %d H*p, cg_kernels %d, %.1f us per iteration (%.1f - %.1f); "
+                "option 1: status %d, %d H*p, cg_kernels %d, %.1f us per iteration (%.1f - %.1f); %.2fx, %s"
+                % (label, d, n, mA, seen[0][0], seen[0][2], seen[0][3], med[0], min(times[0]), max(times[0]),
+                   seen[1][0], seen[1][2], seen[1][3], med[1], min(times[1]), max(times[1]), med[0] / med[1], verdict))
+            if mA:
+                cons.close()
+        H.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(LINES) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="config 2 and 3 only, no Cauchy search (rocprofv3 runs)")
+    ap.add_argument("--cg-fused", action="store_true", help="option gram_cg_fused 0 / 1 alternated on Gram-form handles")
+    ap.add_argument("--one", action="store_true", help="with --cg-fused: two calls on the config-5 shape with the option on, nothing else")
     args = ap.parse_args()
     bh.init(0)
+    if args.cg_fused:
+        cg_fused_mode(args)
+        return
     shapes = [("config 2", 8192, 1024), ("config 3", 65536, 4096)]
     if not args.quick:
         shapes += [("n = 8192", 32768, 8192), ("n = 16384", 16384, 16384)]
