@@ -114,6 +114,7 @@ struct Ctx {
     int64_t opt_cauchy_image = 1;
     int64_t opt_cauchy_image_max_ma = 64;   // ... and with up to this many linear equalities (0..64)
     int64_t opt_cauchy_fused = 1;           // box constraints, one rank, row-space form: ONE kernel per breakpoint (cauchy_fused_kernel)
+    int64_t opt_cauchy_gram_eq = 0;         // Gram-form handle, 1 <= mA <= 64, one rank: the search with linear equalities from G (cauchy_gram_eq_kernel)
     int64_t opt_cauchy_gram = 0;            // Gram-form handle, box constraints, one rank: the whole search from G in one launch (cauchy_gram_kernel)
     int64_t opt_linv_refine = 1;            // explicit-inverse projection (three-kernel CG iteration): one step of iterative refinement of y
     int64_t opt_cauchy_gemm = 1;            // B = J D A' of that form in one sweep on the matrix cores (0: mA J v sweeps over masked rows of A)
@@ -414,6 +415,8 @@ struct bh_hess {
     bool G_valid = false;          // G belongs to the current J and to G_mu
     double G_mu = 0.0;             // the mu G was built with
     int64_t gram_builds = 0;
+    double* geq = nullptr;         // (1 + mA) x ld: a = G D g and B = G D A' of the Cauchy search with equalities from G (lazy, grown on demand)
+    int64_t geq_doubles = 0;
 };
 
 struct bh_proj {
@@ -1432,6 +1435,11 @@ int32_t bh_set_option(const char* key, int64_t value) {
     if (!strcmp(key, "chol_downdate")) { g_ctx.opt_chol_downdate = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "cauchy_image")) { g_ctx.opt_cauchy_image = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "cauchy_gram")) { g_ctx.opt_cauchy_gram = value ? 1 : 0; return BH_OK; }
+    if (!strcmp(key, "cauchy_gram_eq")) {
+        if (value != 0 && value != 1) return fail(BH_ERR_INVALID_ARG, "cauchy_gram_eq is 0 or 1");
+        g_ctx.opt_cauchy_gram_eq = value;
+        return BH_OK;
+    }
     if (!strcmp(key, "gram_cg_fused")) {
         // selects a device path of the product: like every product-path call it needs bh_init (switching it off never fails)
         if (value != 0) BH_REQUIRE_INIT();
@@ -1883,9 +1891,9 @@ int32_t bh_hess_set_mu(bh_hess* H, double mu) {
 static void gram_free(bh_hess* H) {
     if (H->G || H->gpart) {
         if (g_ctx.init) (void)hipStreamSynchronize(g_ctx.stream);   // launches still reading G may be queued
-        dev_free(H->G); dev_free(H->gpart);
+        dev_free(H->G); dev_free(H->gpart); dev_free(H->geq);
     }
-    H->G = nullptr; H->gpart = nullptr;
+    H->G = nullptr; H->gpart = nullptr; H->geq = nullptr; H->geq_doubles = 0;
     H->G_valid = false;
 }
 
@@ -1942,7 +1950,7 @@ int32_t bh_hess_destroy(bh_hess* H) {
     }
     dev_free(H->vpad); dev_free(H->zpad); dev_free(H->upad); dev_free(H->tbuf); dev_free(H->timg); dev_free(H->timg_gen);
     dev_free(H->partials); dev_free(H->sq_partials); dev_free(H->scalar);
-    dev_free(H->G); dev_free(H->gpart);
+    dev_free(H->G); dev_free(H->gpart); dev_free(H->geq);
     for (auto e : H->ev) if (e) (void)hipEventDestroy(e);
     delete H;
     return BH_OK;
@@ -2232,6 +2240,9 @@ static int launch_batch_size(const bh_hess* H) {
 // The first batch is sized by the previous call on the handle (consecutive subproblems of a minor loop behave alike):
 // an exact prediction means no gated launches and no host round trip inside the loop at all.
 constexpr int kFirstBatchCap = 32;
+// bh_cauchy_step, option cauchy_gram_eq: passes between two formations of a = G D g, B = G D A' from the device-side mask
+// (the smallest power of two at which a formation costs at most 5 % of the passes in between: DESIGN.md §8 f-5)
+constexpr int kCauchyGramEqRefresh = 128;
 constexpr int kDowndateRefresh = 8;     // bh_cauchy_step, chol_downdate = 1: breakpoints between two from-scratch factorisations
 
 // Launches the whole projected_cg on device vectors and returns once the host has seen the loop finish (the stream may
@@ -3157,7 +3168,11 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     // Gram-form handle, box constraints, one rank, option "cauchy_gram": init -> G d -> cauchy_gram_kernel, the whole search in one
     // launch (bh_cauchygram.hip.h).  Any other case takes the path it takes without the option.
     const bool gram_search = g_ctx.opt_cauchy_gram != 0 && H->form == BH_HESS_GRAM && mA == 0 && !comm_active();
-    const bool image = !gram_search && g_ctx.opt_cauchy_image != 0 &&
+    // Gram-form handle, 1 <= mA <= 64, one rank, option "cauchy_gram_eq": the linear-equality form in the column space of G
+    // (bh_cauchygrameq.hip.h) — a = G D g, B = G D A' from one G v launch and one GEMM over n rows, re-formed every
+    // kCauchyGramEqRefresh-th pass; per pass [factor + solves: y] -> [Hd = -a - B y | d = P(-g) | t_fresh] -> [decision from Hd].
+    const bool gram_eq = g_ctx.opt_cauchy_gram_eq != 0 && H->form == BH_HESS_GRAM && mA >= 1 && mA <= 64 && !comm_active() && P->ldA == H->ld;
+    const bool image = !gram_search && !gram_eq && g_ctx.opt_cauchy_image != 0 &&
                        (mA == 0 || mA <= g_ctx.opt_cauchy_image_max_ma || (mA <= 64 && P->last_cauchy_passes > 4 * (1 + mA)));
     const bool image_gen = image && mA > 0;
     // ... and there ONE kernel per breakpoint: the decision of pass k-1 in the prologue of the row kernel of pass k (cauchy_fused_kernel)
@@ -3184,6 +3199,14 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
             BH_TRY(dev_alloc(&H->timg_gen, (int64_t)(1 + mA) * img_cap));
             H->timg_gen_doubles = (int64_t)(1 + mA) * img_cap;
         }
+    }
+
+    if (gram_eq && H->geq_doubles < (int64_t)(1 + mA) * H->ld) {
+        if (H->geq) BH_HIP(hipStreamSynchronize(s));              // (launches of an earlier search may still be queued)
+        dev_free(H->geq);
+        H->geq = nullptr; H->geq_doubles = 0;
+        BH_TRY(dev_alloc(&H->geq, (int64_t)(1 + mA) * H->ld));
+        H->geq_doubles = (int64_t)(1 + mA) * H->ld;
     }
 
     CauchyPass* pp = nullptr;
@@ -3279,6 +3302,39 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
             BH_HIP(hipGetLastError());
             return BH_OK;
         }
+        if (gram_eq) {
+            ProjArgs pa = proj_args(P, c.d_state, true, true);
+            if (index > 0) {
+                P->linv_valid = false;
+                hipLaunchKernelGGL(cauchy_factor_solve_kernel, dim3(1), dim3(256), 0, s, P->M, P->Lr, mA, P->info, pa, (const double*)c.r,
+                                   (const double*)P->tpart, (const CgState*)c.d_state);
+            } else {
+                hipLaunchKernelGGL(proj_left_mul_kernel, dim3(mA), dim3(256), 0, s, pa, (const double*)c.r);     // t (:86-98), then y
+                hipLaunchKernelGGL(trsv_small_kernel, dim3(1), dim3(256), 0, s, pa);
+            }
+            BH_HIP(hipGetLastError());
+            // a = G D g: one G v launch over the masked g (G rebuilt first when it is stale).  B = G D A' (n x mA): the GEMM of the
+            // row-space form over the n rows of G.  Pass 0, and again every kCauchyGramEqRefresh-th pass from the device-side mask,
+            // which by then holds the variable fixed by the decision in between: the row kernel behind a formation applies no update.
+            const bool form_ab = (index % kCauchyGramEqRefresh) == 0;
+            if (form_ab) {
+                const int mgrid = std::max(1, std::min((int)((n + 255) / 256), 1024));
+                hipLaunchKernelGGL(proj_mask_kernel, dim3(mgrid), dim3(256), 0, s, a.g, H->vpad, (const int*)P->fixrank, (int)n, (const CgState*)c.d_state);
+                BH_TRY(launch_hmul(H, H->vpad, H->geq, c.d_state, -1));
+                hipLaunchKernelGGL(image_b_mfma_kernel, dim3((unsigned)((n + 127) / 128)), dim3(256), 0, s, (const double*)H->G, H->ld, n,
+                                   (const double*)P->Ad, P->ldA, mA, (const int*)P->fixrank, H->geq + H->ld, H->ld, (const CgState*)c.d_state);
+                BH_HIP(hipGetLastError());
+            }
+            CauchyGramEqArgs ga{};
+            ga.st = c.d_state; ga.G = H->G; ga.ld = H->ld; ga.n = (int)n; ga.mA = mA; ga.a = H->geq; ga.B = H->geq + H->ld;
+            ga.A = P->Ad; ga.ldA = P->ldA; ga.tw = P->tw; ga.g = a.g; ga.Hd = c.Hp; ga.fresh = form_ab ? 1 : 0;
+            const int rblocks = (int)(H->ld / 16), dblocks = ((int)(n + 1) / 2 + 63) / 64;
+            hipLaunchKernelGGL(cauchy_gram_eq_kernel, dim3(rblocks + dblocks + mA), dim3(256), 0, s, ga, rblocks, dblocks, pa, (const double*)c.r,
+                               c.p, P->tpart);
+            hipLaunchKernelGGL(cauchy_advance_kernel, dim3(1), dim3(CA_T), 0, s, a);
+            BH_HIP(hipGetLastError());
+            return BH_OK;
+        }
         if (index > 0 && mA > 0) {
             // chol_downdate = 1 only has a case where refactoring is expensive (mA > 64: blocked factorisation, 0.21 ms at mA = 256);
             // up to 64 rows the register-panel Cholesky (18.5 us) costs what the rank-one downdate costs (20 us), so the factor is
@@ -3319,7 +3375,7 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
         launched = max_pass;                                        // the kernel publishes once, when its loop has ended
     }
     // image-space passes take ~17 us: keep a deeper queue ahead of the GPU (over RCCL every over-launched pass costs a collective)
-    const int batch = !image ? launch_batch_size(H) : (comm_active() && !use_peer_path()) ? 4 : 8;
+    const int batch = (!image && !gram_eq) ? launch_batch_size(H) : (comm_active() && !use_peer_path()) ? 4 : 8;
     // (fused form: launch k carries decision k-1, so `launched` launches stand for launched - 1 passes)
     const int off = fused ? 1 : 0;
     const int max_launch = max_pass + off;
@@ -3345,9 +3401,11 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     BH_TRY(fetch_vec(s_out, fused ? sbuf[mw.n_hmul & 1] : c.w, n, dev));
     int info_host = 0;
     BH_TRY(adopt_device_mask(P, fix_chunks_out, &info_host));     // drains the stream; canonical fixrank / fixidx, P->nfix
-    if (!image && !gram_search) H->stats.n_hmul += mw.n_hmul;  // (image-space search: passes, not sweeps over J)
+    if (!image && !gram_search && !gram_eq) H->stats.n_hmul += mw.n_hmul;  // (image-space search: passes, not sweeps over J)
+    // from G with equalities: the G v launches that ran — pass 0 and every kCauchyGramEqRefresh-th pass (those enqueued behind the end are gated off)
+    if (gram_eq) H->stats.n_hmul += 1 + std::max(mw.n_hmul - 1, 0) / kCauchyGramEqRefresh;
     P->last_cauchy_passes = mw.n_hmul;
-    P->last_cauchy_form = gram_search ? 3 : !image ? 0 : image_gen ? 2 : 1;
+    P->last_cauchy_form = gram_search ? 3 : gram_eq ? 4 : !image ? 0 : image_gen ? 2 : 1;
     P->last_cauchy_launches = (int)(g_kernel_launches - launches_in);
     if (!mw.done) return fail(BH_ERR_HIP, "internal: Cauchy loop did not terminate");
     if (n_breakpoints) *n_breakpoints = mw.iter;

@@ -215,8 +215,9 @@ __global__ __launch_bounds__(256) void cauchy_gen_rows_and_d_kernel(CauchyImgGen
 // Fixed order of accumulation: bit-reproducible.
 __global__ __launch_bounds__(256) void image_b_mfma_kernel(const double* __restrict__ J, int64_t ld, int64_t nrows, const double* __restrict__ A,
                                                            int64_t ldA, int mA, const int* __restrict__ fixrank, double* __restrict__ B,
-                                                           int64_t rows_cap) {
+                                                           int64_t rows_cap, const CgState* gate = nullptr) {
     __shared__ double2 atile[2][4][2][64];            // [buffer][output tile][column pair 01 / 23][lane]
+    if (gate != nullptr && gate->done) return;        // (a re-formation enqueued behind the end of the loop it belongs to)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t strip = ((int64_t)blockIdx.x * 4 + wave) * 32;         // (waves past the last row still take part in the barriers)
     const int ri = lane & 15, kq = lane >> 4;

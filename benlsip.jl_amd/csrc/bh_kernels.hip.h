@@ -24,6 +24,7 @@
 #include "bh_proj.hip.h"
 #include "bh_cauchy.hip.h"
 #include "bh_cauchygram.hip.h"
+#include "bh_cauchygrameq.hip.h"
 #include "bh_minor.hip.h"
 #include "bh_gngram.hip.h"
 #include "bh_gramcg.hip.h"

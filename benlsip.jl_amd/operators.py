@@ -460,7 +460,8 @@ def cauchy_step(x, g, H, lincons, delta, full_output=False):
 
 def cauchy_info(lincons):
     """``bh_cauchy_info``: ``(form, n_launches)`` of the last ``cauchy_step`` on ``lincons`` — form 0 = one ``H*d`` per breakpoint,
-    1 = row space of ``J`` (box), 2 = row space of ``J`` with equalities, 3 = from ``G`` in one launch (option ``cauchy_gram``)."""
+    1 = row space of ``J`` (box), 2 = row space of ``J`` with equalities, 3 = from ``G`` in one launch (option ``cauchy_gram``),
+    4 = from ``G`` with linear equalities (option ``cauchy_gram_eq``)."""
     form, nl = ct.c_int32(-1), ct.c_int32(0)
     check(_lib.lib().bh_cauchy_info(lincons._h, ct.byref(form), ct.byref(nl)), "bh_cauchy_info")
     return form.value, nl.value
@@ -486,8 +487,8 @@ def resid_sqnorm(rx):
 
 def set_option(key, value):
     """``bh_set_option``: process-wide integer options (the list with defaults is in include/benlsip_hip.h), e.g. ``cg_fused``,
-    ``proj_form``, ``cauchy_image``, ``cauchy_gram`` and ``gram_cg_fused`` (fused two- / three-kernel CG iteration on a
-    Gram-form handle, default 0)."""
+    ``proj_form``, ``cauchy_image``, ``cauchy_gram``, ``cauchy_gram_eq`` (Cauchy search with 1..64 linear equalities from ``G`` on a
+    Gram-form handle, default 0) and ``gram_cg_fused`` (fused two- / three-kernel CG iteration on a Gram-form handle, default 0)."""
     check(_lib.lib().bh_set_option(key.encode(), int(value)), "bh_set_option(%s)" % key)
 
 

@@ -168,10 +168,12 @@ int32_t bh_hess_destroy(bh_hess* H);
  *   "gram_cg_fused" = 1 the fused shape, stats.cg_kernels = 2 or 3, the same dot(p, H*p) summed per workgroup) and the H*d form of
  *   cauchy_step(...) — src/basic_tralcnlss.jl:574-639 (cauchy_image = 0, or more linear equalities than its row-space form takes);
  *   with option "cauchy_gram" = 1 also the whole box-constrained search of cauchy_step(...) (no linear equalities, one rank):
- *   Hd = G d once, then one row of G per breakpoint inside ONE launch (cauchy_gram_kernel).
+ *   Hd = G d once, then one row of G per breakpoint inside ONE launch (cauchy_gram_kernel); with option "cauchy_gram_eq" = 1 the
+ *   search with 1..64 linear equalities (one rank): Hd = -a - B y from a = G D g (n) and B = G D A' (n x mA), one row of G per
+ *   breakpoint, a and B formed again from G every 128th pass (cauchy_gram_eq_kernel; bh_cauchy_info form 4).
  *   Still reading J: vthv(H, v) — src/basic_tralcnlss.jl:92-96 and bh_linesearch (||Jv||^2_W, never negative), bh_jv, bh_jtv,
- *   bh_grad, and the row-space Cauchy search (cauchy_image = 1, up to 64 equalities; with box constraints only while
- *   "cauchy_gram" = 0).
+ *   bh_grad, and the row-space Cauchy search (cauchy_image = 1; with box constraints only while "cauchy_gram" = 0, with up to
+ *   64 equalities only while "cauchy_gram_eq" = 0).
  * bh_hess_set_form: setting the current form is a no-op; BH_HESS_IMPLICIT frees G; BH_ERR_INVALID_ARG for another value;
  * BH_ERR_UNSUPPORTED for n > 16384 (G would exceed 2 GiB) or while a communicator with more than one rank is active; a failed
  * allocation returns BH_ERR_HIP and leaves the handle in the implicit form.  While the Gram form is on, stats.bytes_per_hmul is
@@ -271,7 +273,8 @@ int32_t bh_linesearch(bh_hess* H, bh_proj* P, const double* g_model, const doubl
 int32_t bh_cauchy_step(bh_hess* H, bh_proj* P, const double* x, const double* g, const double* xlow, const double* xupp,
                        double delta, double* s_out, uint64_t* fix_chunks_out, int32_t* n_breakpoints, int32_t* n_hmul);
 /* Form and launch count of the last bh_cauchy_step(_dev) on this bh_proj:
- *   form 0 = one H*d per breakpoint, 1 = row space of J (box), 2 = row space of J with equalities, 3 = from G in one launch
+ *   form 0 = one H*d per breakpoint, 1 = row space of J (box), 2 = row space of J with equalities, 3 = from G in one launch,
+ *   form 4 = from G with linear equalities (option "cauchy_gram_eq")
  *   n_launches = kernels enqueued by that call (over-launched prologue-only passes included).
  * BH_ERR_PRECONDITION before the first search on the handle. */
 int32_t bh_cauchy_info(const bh_proj* P, int32_t* form, int32_t* n_launches);
@@ -390,6 +393,12 @@ int32_t bh_stats_reset(bh_hess* H);
  *                        search in ONE launch from G (init -> G d -> cauchy_gram_kernel: Hd downdated by one row of G per breakpoint, the
  *                        loop runs on the device; the launch count does not depend on the number of breakpoints).  Any other handle or
  *                        constraint set takes the path it takes with 0.  bh_cauchy_info tells which form ran
+ *   "cauchy_gram_eq" [0] bh_cauchy_step(_dev) on a handle in the Gram form with 1..64 linear equalities, one rank, lineq image with the
+ *                        handle's leading dimension: the linear-equality search in the column space of G (form 4) — a = G D g and
+ *                        B = G D A' from one G v launch and one GEMM over n rows, one contiguous row of G per breakpoint, three launches
+ *                        per pass, a and B formed again every 128th pass; stats.n_hmul grows by those G v launches, n_jv by nothing.
+ *                        Values 0 / 1 (another value: BH_ERR_INVALID_ARG).  Independent of "cauchy_gram", "cauchy_image" and
+ *                        "cauchy_image_max_ma".  Any other handle or constraint set takes the path it takes with 0
  *   "gram_cg_fused"  [0] bh_pcg*, bh_minor_iterate* on a handle in the Gram form (one rank by construction), independent of "cg_fused":
  *                        TWO kernels per CG iteration with box constraints (gram_cg_kernel: G·v with p_j, beta and the exit test formed
  *                        in its prologue, H*p stored as one vector next to per-workgroup partials of dot(p, H*p); then

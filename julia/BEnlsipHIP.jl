@@ -79,6 +79,15 @@ function gram_cauchy!(flag::Bool = true)
     return flag
 end
 
+# The Cauchy search with 1..64 linear equalities from G (bh_set_option("cauchy_gram_eq", 1), DESIGN.md §8 f-5): opt-in, under the same
+# two conditions as gram_cauchy!, on one rank; a and B of its row-space form are kept in the column space of G (n rows instead of
+# d + q) and formed again every 128th pass.  Every other case takes the path it takes without it.
+#     BEnlsipHIP.gram_cauchy_eq!(true)
+function gram_cauchy_eq!(flag::Bool = true)
+    check(ccall((:bh_set_option, libbh), Int32, (Cstring, Int64), "cauchy_gram_eq", flag ? 1 : 0), "bh_set_option(cauchy_gram_eq)")
+    return flag
+end
+
 function product_handle(H::BEnlsip.AlHessian{Float64})
     h = handle(H)
     GRAM_HESSIAN[] && check(ccall((:bh_hess_set_form, libbh), Int32, (Ptr{Cvoid}, Int32), h, 1), "bh_hess_set_form")   # BH_HESS_GRAM
