@@ -337,10 +337,10 @@ def linesearch(g_model, H, w, w_l, w_u, fix_bounds, vthv_fn: Callable = vthv) ->
         neg = free & (w < 0)
         pos = free & (w > 0)
         if neg.any():
-            alpha_allowed = min(alpha_allowed, float(np.min(w_l[neg] / w[neg])))  # :783
+            alpha_allowed = _julia_min(alpha_allowed, float(np.min(w_l[neg] / w[neg])))  # :783 (np.min propagates NaN like Julia's min)
         if pos.any():
-            alpha_allowed = min(alpha_allowed, float(np.min(w_u[pos] / w[pos])))  # :785
-    return min(alpha_opt, alpha_allowed)              # :790
+            alpha_allowed = _julia_min(alpha_allowed, float(np.min(w_u[pos] / w[pos])))  # :785
+    return _julia_min(alpha_opt, alpha_allowed)       # :790
 
 
 # --------------------------------------------------------------------------- #
