@@ -113,6 +113,7 @@ struct Ctx {
     // one J v sweep at the start, then no sweep over J per breakpoint), 0 = one H*d sweep per breakpoint as the reference does
     int64_t opt_cauchy_image = 1;
     int64_t opt_cauchy_image_max_ma = 64;   // ... and with up to this many linear equalities (0..64)
+    int64_t opt_cauchy_image_refresh = 0;   // row-space search, one rank: R >= 1 forms t_d, t_s (a, B, t_s) again from J every R-th pass (0: never)
     int64_t opt_cauchy_fused = 1;           // box constraints, one rank, row-space form: ONE kernel per breakpoint (cauchy_fused_kernel)
     int64_t opt_cauchy_gram_eq = 0;         // Gram-form handle, 1 <= mA <= 64, one rank: the search with linear equalities from G (cauchy_gram_eq_kernel)
     int64_t opt_cauchy_gram = 0;            // Gram-form handle, box constraints, one rank: the whole search from G in one launch (cauchy_gram_kernel)
@@ -171,6 +172,7 @@ struct Ctx {
     int64_t rbuf_cap = 0;
     int live_hess = 0;               // bh_hess handles alive (a handle bakes in this rank's share of C: see bh_comm_init)
     // dynamic-LDS ceilings already raised on this device (hipFuncSetAttribute); reset by bh_shutdown
+    bool reform_vlds_attr_set = false;   // cauchy_reform_kernel<512,16,1,VL>
     bool vlds_attr_set = false;      // row_stream_kernel<512,16,1,FUSED,...,VL>
     bool cgp_vlds_attr_set = false;  // ... and its two CG-prologue symbols
     bool trsm_lds_granted = false;   // chol_trsm_kernel
@@ -332,6 +334,29 @@ void launch_row_stream_cgp(int cfg, const RowStreamArgs& a, int grid, hipStream_
             }
             if (expect_stop) hipLaunchKernelGGL((row_stream_kernel<512, 16, 1, MODE_FUSED, 1, 1, 1, 2>), dim3(grid), dim3(512), lds, s, a);
             else hipLaunchKernelGGL((row_stream_kernel<512, 16, 1, MODE_FUSED, 1, 1, 1, 1>), dim3(grid), dim3(512), lds, s, a);
+            break;
+        }
+    }
+}
+
+// Option cauchy_image_refresh, one-kernel-per-breakpoint form: t_d = J~ d, t_s = J~ s_c and their sums in one sweep (cauchy_reform_kernel),
+// the geometries of kRsConfigs.  n <= 8192: both vector slices in registers; above, the slice of d in LDS (128 KiB, asked for once).
+void launch_cauchy_reform(int cfg, const CauchyReformArgs& a, int grid, hipStream_t s) {
+    switch (cfg) {
+        case 0: hipLaunchKernelGGL((cauchy_reform_kernel<64, 1, 8, 0>), dim3(grid), dim3(64), 0, s, a); break;
+        case 1: hipLaunchKernelGGL((cauchy_reform_kernel<256, 1, 8, 0>), dim3(grid), dim3(256), 0, s, a); break;
+        case 2: hipLaunchKernelGGL((cauchy_reform_kernel<256, 2, 8, 0>), dim3(grid), dim3(256), 0, s, a); break;
+        case 3: hipLaunchKernelGGL((cauchy_reform_kernel<256, 4, 4, 0>), dim3(grid), dim3(256), 0, s, a); break;
+        case 4: hipLaunchKernelGGL((cauchy_reform_kernel<256, 8, 4, 0>), dim3(grid), dim3(256), 0, s, a); break;
+        case 5: hipLaunchKernelGGL((cauchy_reform_kernel<512, 8, 2, 0>), dim3(grid), dim3(512), 0, s, a); break;
+        default: {
+            constexpr size_t lds = (size_t)512 * 16 * sizeof(double2);
+            if (!g_ctx.reform_vlds_attr_set) {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cauchy_reform_kernel<512, 16, 1, 1>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                g_ctx.reform_vlds_attr_set = true;
+            }
+            hipLaunchKernelGGL((cauchy_reform_kernel<512, 16, 1, 1>), dim3(grid), dim3(512), lds, s, a);
             break;
         }
     }
@@ -725,12 +750,13 @@ int32_t launch_hmul(bh_hess* H, const double* v_pad, double* z_out, const CgStat
     return reduce_slabs(H, grid, z_out, state);
 }
 
-int32_t launch_jv(bh_hess* H, const double* v_pad, double* t_out, bool with_c_rows, double* sq_out_scalar) {
+// (state: NULL, or the launches are skipped when state->done — a sweep enqueued behind the end of the loop it belongs to)
+int32_t launch_jv(bh_hess* H, const double* v_pad, double* t_out, bool with_c_rows, double* sq_out_scalar, const CgState* state = nullptr) {
     BH_TRY(hess_ready(H));
     const int64_t nrows = H->d + (with_c_rows ? H->q_eff : 0);
     if (multi_panel(H)) {
         double* t = t_out ? t_out : H->tbuf;
-        BH_TRY(launch_jv_panels(H, v_pad, t, nrows, nullptr));
+        BH_TRY(launch_jv_panels(H, v_pad, t, nrows, state));
         if (sq_out_scalar)
             hipLaunchKernelGGL(weighted_sqsum_kernel, dim3(1), dim3(1024), 0, g_ctx.stream, (const double*)t, nrows, H->d, H->mu, sq_out_scalar);
         BH_HIP(hipGetLastError());
@@ -738,7 +764,7 @@ int32_t launch_jv(bh_hess* H, const double* v_pad, double* t_out, bool with_c_ro
     }
     const int cfg = pick_config(H->nchunks);
     const int grid = grid_for(cfg, nrows);
-    RowStreamArgs a = rs_args(H, nrows, nullptr);
+    RowStreamArgs a = rs_args(H, nrows, state);
     a.v = v_pad; a.t_out = t_out;
     a.sq_partials = sq_out_scalar ? H->sq_partials : nullptr;
     launch_row_stream(cfg, MODE_JV, a, grid, g_ctx.stream);
@@ -1384,7 +1410,7 @@ int32_t bh_shutdown(void) {
     if (g_ctx.own_stream) (void)hipStreamDestroy(g_ctx.own_stream);
     g_ctx.own_stream = nullptr; g_ctx.stream = nullptr;
     if (g_pin.base) { (void)hipHostFree(g_pin.base); g_pin = PinArena(); }
-    g_ctx.vlds_attr_set = false; g_ctx.cgp_vlds_attr_set = false; g_ctx.trsm_lds_granted = false; g_ctx.trsv_lds_granted = 0;
+    g_ctx.vlds_attr_set = false; g_ctx.cgp_vlds_attr_set = false; g_ctx.reform_vlds_attr_set = false; g_ctx.trsm_lds_granted = false; g_ctx.trsv_lds_granted = 0;
     g_ctx.init = false; g_ctx.rank = 0; g_ctx.nranks = 1;
     return BH_OK;
 }
@@ -1445,6 +1471,11 @@ int32_t bh_set_option(const char* key, int64_t value) {
         if (value != 0) BH_REQUIRE_INIT();
         if (value != 0 && value != 1) return fail(BH_ERR_INVALID_ARG, "gram_cg_fused is 0 or 1");
         g_ctx.opt_gram_cg_fused = value;
+        return BH_OK;
+    }
+    if (!strcmp(key, "cauchy_image_refresh")) {
+        if (value < 0) return fail(BH_ERR_INVALID_ARG, "cauchy_image_refresh is 0 (never) or the number of passes between two re-formations");
+        g_ctx.opt_cauchy_image_refresh = value;
         return BH_OK;
     }
     if (!strcmp(key, "cauchy_fused")) { g_ctx.opt_cauchy_fused = value ? 1 : 0; return BH_OK; }
@@ -3177,7 +3208,18 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     const bool image_gen = image && mA > 0;
     // ... and there ONE kernel per breakpoint: the decision of pass k-1 in the prologue of the row kernel of pass k (cauchy_fused_kernel)
     const bool fused = image && !image_gen && !comm_active() && g_ctx.opt_cauchy_fused != 0;
+    // Option cauchy_image_refresh = R >= 1 (one rank): at every pass index that is a positive multiple of R the images are formed again
+    // from J and the device-side state, behind the `done` gate; the other passes are unchanged.  Several ranks: ignored.
+    //   one kernel per breakpoint: launch k -> [cauchy_fused_kernel, decide_only: decision k-1] [cauchy_reform_kernel: t_d, t_s, sums];
+    //                              a J wider than the register-resident kernels hold (n > 16384) keeps its carried images
+    //   two-kernel box form:       [J v of d] [J v of s_c] before cauchy_image_kernel(fresh = 1)
+    //   with equalities:           [mask g, J v: a] [B: the GEMM or mA masked sweeps] [J v of s_c] before the row kernel (fresh = 1)
+    const int refresh = (image && !comm_active() && !(fused && multi_panel(H))) ? (int)std::min<int64_t>(g_ctx.opt_cauchy_image_refresh, 0xfffff) : 0;
+    auto reforms_at = [&](int index) { return refresh > 0 && index > 0 && (index % refresh) == 0; };
+    int reform_sweeps = 0;                                            // sweeps over J of one re-formation, for stats.n_jv
     const int64_t img_rows = H->d + H->q_eff;
+    const int reform_cfg = pick_config(std::min<int>(H->nchunks, (int)kMaxChunks));
+    const int reform_grid = std::min(kCauchyFusedGrid, grid_for(reform_cfg, img_rows));
     const int img_grid = (int)std::max<int64_t>(1, std::min<int64_t>(fused ? kCauchyFusedGrid : kCauchyImgGrid, (img_rows + 255) / 256));
     // (fewer, fatter workgroups measured slower: docs/design_history_r3.md)
     const int fused_grid = (int)std::max<int64_t>(1, std::min<int64_t>(kCauchyFusedGrid, (img_rows + CA_T - 1) / CA_T));
@@ -3229,8 +3271,23 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
             fa.fixpass = a.fixpass; fa.fixrank = P->fixrank; fa.n = (int)n; fa.nmm = a.nmm;
             fa.J = H->Jd; fa.ld = H->ld; fa.nrows = img_rows; fa.d_rows = H->d; fa.mu = H->mu;
             fa.td = H->timg; fa.ts = H->timg + img_cap;
-            fa.part_in = part_pp[(index - 1) & 1]; fa.Gin = index == 1 ? img_grid : fused_grid; fa.part_out = part_pp[index & 1];
+            fa.part_in = part_pp[(index - 1) & 1]; fa.Gin = index == 1 ? img_grid : reforms_at(index - 1) ? reform_grid : fused_grid;
+            fa.part_out = part_pp[index & 1];
             fa.mirror = a.mirror; fa.tag = a.tag;
+            if (reforms_at(index)) {
+                // decision index-1 alone (every group of 64 elements of s_c has its owner at any grid), then both images from J
+                fa.decide_only = 1;
+                const int dec_grid = (int)std::max<int64_t>(1, std::min<int64_t>(fused_grid, (n + 63) / 64));
+                hipLaunchKernelGGL(cauchy_fused_kernel, dim3(dec_grid), dim3(CA_T), 0, s, fa);
+                CauchyReformArgs ra{};
+                ra.gate = pp + (index & 1); ra.k = index; ra.g = a.g; ra.fixpass = a.fixpass; ra.n = (int)n; ra.s = sbuf[index & 1];
+                ra.J = H->Jd; ra.ld = H->ld; ra.nrows = img_rows; ra.d_rows = H->d; ra.mu = H->mu; ra.nchunks = H->nchunks;
+                ra.td = fa.td; ra.ts = fa.ts; ra.part = part_pp[index & 1];
+                launch_cauchy_reform(reform_cfg, ra, reform_grid, s);
+                reform_sweeps = 1;
+                BH_HIP(hipGetLastError());
+                return BH_OK;
+            }
             hipLaunchKernelGGL(cauchy_fused_kernel, dim3(fused_grid), dim3(CA_T), 0, s, fa);
             BH_HIP(hipGetLastError());
             return BH_OK;
@@ -3250,6 +3307,7 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
             CauchyImgArgs ia{};
             ia.st = c.d_state; ia.J = H->Jd; ia.ld = H->ld; ia.nrows = img_rows; ia.d_rows = H->d; ia.mu = H->mu;
             ia.td = H->timg; ia.ts = H->timg + rows_cap; ia.part = H->timg + 2 * rows_cap; ia.first = index == 0 ? 1 : 0;
+            ia.fresh = reforms_at(index) ? 1 : 0;
             if (image_gen) {
                 // factor of the current active set and y = (A_free A_free')^{-1} A_free(-g) (left in P->tw), as in the sweeping form
                 // Three launches per pass (image_gen implies mA <= 64): [downdate + refactorisation + right-hand side + the two solves: y]
@@ -3264,21 +3322,28 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
                     hipLaunchKernelGGL(trsv_small_kernel, dim3(1), dim3(256), 0, s, pa);
                 }
                 BH_HIP(hipGetLastError());
-                if (index == 0) {
+                if (index == 0 || ia.fresh) {
+                    // (index > 0: the re-formation of option cauchy_image_refresh, from the device-side mask — which holds the variable
+                    // the decision of pass index-1 fixed — and gated by `done`; t_s = J~ s_c from the s_c that decision left)
+                    const CgState* gate = index == 0 ? nullptr : (const CgState*)c.d_state;
                     // a = J~ D g: one J v sweep over the masked g.  B = J~ D A' (rows x mA): ONE sweep on the matrix cores
                     // (image_b_mfma_kernel) when the images share their leading dimension, else mA J v sweeps over masked rows of A
                     const int mgrid = std::max(1, std::min((int)((n + 255) / 256), 1024));
                     const bool gemm = g_ctx.opt_cauchy_gemm != 0 && P->ldA == H->ld;
                     for (int j = -1; j < (gemm ? 0 : mA); ++j) {
                         const double* src = (j < 0) ? a.g : (const double*)(P->Ad + (int64_t)j * P->ldA);
-                        hipLaunchKernelGGL(proj_mask_kernel, dim3(mgrid), dim3(256), 0, s, src, H->vpad, (const int*)P->fixrank, (int)n, (const CgState*)nullptr);
-                        BH_TRY(launch_jv(H, H->vpad, H->timg_gen + (int64_t)(j + 1) * rows_cap, true, nullptr));
-                        H->stats.n_jv += 1;
+                        hipLaunchKernelGGL(proj_mask_kernel, dim3(mgrid), dim3(256), 0, s, src, H->vpad, (const int*)P->fixrank, (int)n, gate);
+                        BH_TRY(launch_jv(H, H->vpad, H->timg_gen + (int64_t)(j + 1) * rows_cap, true, nullptr, gate));
+                        if (index == 0) H->stats.n_jv += 1;
                     }
                     if (gemm && img_rows > 0) {                 // (a rank without rows has no rows of B)
                         hipLaunchKernelGGL(image_b_mfma_kernel, dim3((unsigned)((img_rows + 127) / 128)), dim3(256), 0, s, (const double*)H->Jd, H->ld,
-                                           img_rows, (const double*)P->Ad, P->ldA, mA, (const int*)P->fixrank, H->timg_gen + rows_cap, rows_cap);
+                                           img_rows, (const double*)P->Ad, P->ldA, mA, (const int*)P->fixrank, H->timg_gen + rows_cap, rows_cap, gate);
                         BH_HIP(hipGetLastError());
+                    }
+                    if (index > 0) {
+                        BH_TRY(launch_jv(H, c.w, H->timg + rows_cap, true, nullptr, gate));
+                        reform_sweeps = (gemm ? 1 : 1 + mA) + 1;
                     }
                 }
                 CauchyImgGenArgs ga{};
@@ -3291,6 +3356,12 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
                 if (index == 0) {
                     BH_TRY(launch_jv(H, c.p, H->timg, true, nullptr));              // t_d = J~ d_0 (:609 in the row space)
                     H->stats.n_jv += 1;
+                }
+                if (ia.fresh) {
+                    // t_d = J~ d from the d the advance kernel keeps (d[ind] is zero already), t_s = J~ s_c: gated by `done`
+                    BH_TRY(launch_jv(H, c.p, H->timg, true, nullptr, (const CgState*)c.d_state));
+                    BH_TRY(launch_jv(H, c.w, H->timg + rows_cap, true, nullptr, (const CgState*)c.d_state));
+                    reform_sweeps = 2;
                 }
                 hipLaunchKernelGGL(cauchy_image_kernel, dim3(img_grid), dim3(256), 0, s, ia);
             }
@@ -3404,6 +3475,9 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     if (!image && !gram_search && !gram_eq) H->stats.n_hmul += mw.n_hmul;  // (image-space search: passes, not sweeps over J)
     // from G with equalities: the G v launches that ran — pass 0 and every kCauchyGramEqRefresh-th pass (those enqueued behind the end are gated off)
     if (gram_eq) H->stats.n_hmul += 1 + std::max(mw.n_hmul - 1, 0) / kCauchyGramEqRefresh;
+    // option cauchy_image_refresh: the sweeps over J of the re-formations that ran — pass indices R, 2R, ... below the number of passes
+    // (those enqueued behind the end are gated off)
+    if (refresh > 0) H->stats.n_jv += (int64_t)reform_sweeps * (std::max(mw.n_hmul - 1, 0) / refresh);
     P->last_cauchy_passes = mw.n_hmul;
     P->last_cauchy_form = gram_search ? 3 : gram_eq ? 4 : !image ? 0 : image_gen ? 2 : 1;
     P->last_cauchy_launches = (int)(g_kernel_launches - launches_in);

@@ -50,6 +50,8 @@ struct CauchyImgArgs {
     double* td; double* ts;
     double* part;           // [2][gridDim.x]: partial sums of w t_s t_d and of w t_d^2
     int first;              // pass 0: t_d = J d has just been formed by the J v kernel, t_s = 0: no update, only the sums
+    int fresh;              // option cauchy_image_refresh: t_d, t_s (with equalities a, B, t_s) have just been formed again from J for the
+                            // CURRENT d and s_c: no update, only the sums (with equalities: t_d = -a - B y)
 };
 
 // The same with linear equalities (reduced projection form, small mA).  d = P(-g) = -D g - D A'y changes in every free component
@@ -77,7 +79,7 @@ __device__ __forceinline__ void cauchy_image_gen_rows_body(const CauchyImgGenArg
     __shared__ double s_acol[64], s_y[64];
     const int ind = st->status;
     const double theta = st->gamma;
-    const bool upd = !a.first && ind >= 0;
+    const bool upd = !a.first && !a.fresh && ind >= 0;
     if ((int)threadIdx.x < ga.mA) {
         s_acol[threadIdx.x] = upd ? ga.A[(int64_t)threadIdx.x * ga.ldA + ind] : 0.0;
         s_y[threadIdx.x] = ga.tw[threadIdx.x];
@@ -87,7 +89,8 @@ __device__ __forceinline__ void cauchy_image_gen_rows_body(const CauchyImgGenArg
     double acc[2] = {0.0, 0.0};
     for (int64_t i = (int64_t)block * 256 + threadIdx.x; i < a.nrows; i += (int64_t)nblocks * 256) {
         double ts = 0.0;
-        if (!a.first) ts = __dadd_rn(a.ts[i], __dmul_rn(theta, a.td[i]));        // s_c += theta d  with the PREVIOUS d   (:628)
+        if (a.fresh) ts = a.ts[i];                                               // t_s = J~ s_c as just formed
+        else if (!a.first) ts = __dadd_rn(a.ts[i], __dmul_rn(theta, a.td[i]));   // s_c += theta d  with the PREVIOUS d   (:628)
         const double col = upd ? a.J[i * a.ld + ind] : 0.0;
         double ai = ga.a[i];
         if (upd) { ai = __dsub_rn(ai, __dmul_rn(g_ind, col)); ga.a[i] = ai; }
@@ -122,7 +125,7 @@ __device__ __forceinline__ void cauchy_image_gen_body(const CauchyImgGenArgs& ga
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ind = st->status;
     const double theta = st->gamma;
-    const bool upd = !a.first && ind >= 0;
+    const bool upd = !a.first && !a.fresh && ind >= 0;
     if ((int)threadIdx.x < ga.mA) {
         s_acol[threadIdx.x] = upd ? ga.A[(int64_t)threadIdx.x * ga.ldA + ind] : 0.0;
         s_y[threadIdx.x] = ga.tw[threadIdx.x];
@@ -144,7 +147,8 @@ __device__ __forceinline__ void cauchy_image_gen_body(const CauchyImgGenArgs& ga
         double ai = 0.0, ts = 0.0;
         if (wave == 0) {
             ai = ga.a[ic];
-            if (!a.first) ts = __dadd_rn(a.ts[ic], __dmul_rn(theta, a.td[ic]));  // s_c += theta d  with the PREVIOUS d   (:628)
+            if (a.fresh) ts = a.ts[ic];                                          // t_s = J~ s_c as just formed
+            else if (!a.first) ts = __dadd_rn(a.ts[ic], __dmul_rn(theta, a.td[ic]));  // s_c += theta d  with the PREVIOUS d   (:628)
             const double col = upd ? a.J[ic * a.ld + ind] : 0.0;
             s_col[lane] = col;
             if (upd) { ai = __dsub_rn(ai, __dmul_rn(g_ind, col)); if (vrow) ga.a[i] = ai; }
@@ -319,12 +323,16 @@ __global__ __launch_bounds__(256) void cauchy_image_kernel(CauchyImgArgs a) {
     double acc[2] = {0.0, 0.0};
     for (int64_t i = i0; i < a.nrows; i += (int64_t)gridDim.x * 256) {
         double td = (i == i0) ? td0 : a.td[i], ts = 0.0;
-        if (!a.first) {
-            ts = __dadd_rn((i == i0) ? ts0 : a.ts[i], __dmul_rn(theta, td));    // s_c += theta d          (:628)
-            td = __dsub_rn(td, __dmul_rn(dind, a.J[i * a.ld + ind]));            // d[ind] = 0              (:632, box)
-            a.td[i] = td;
+        if (a.fresh) {
+            ts = (i == i0) ? ts0 : a.ts[i];                                     // both images as just formed from J
+        } else {
+            if (!a.first) {
+                ts = __dadd_rn((i == i0) ? ts0 : a.ts[i], __dmul_rn(theta, td));    // s_c += theta d          (:628)
+                td = __dsub_rn(td, __dmul_rn(dind, a.J[i * a.ld + ind]));            // d[ind] = 0              (:632, box)
+                a.td[i] = td;
+            }
+            a.ts[i] = ts;
         }
-        a.ts[i] = ts;
         const double w = (i < a.d_rows) ? 1.0 : a.mu;
         acc[0] = fma(w * ts, td, acc[0]);
         acc[1] = fma(w * td, td, acc[1]);
@@ -539,6 +547,8 @@ struct CauchyFusedArgs {
     const double* part_in; int Gin;          // [2][Gin] from the previous launch
     double* part_out;                        // [2][gridDim.x]
     unsigned long long* mirror; unsigned tag;
+    int decide_only;                         // option cauchy_image_refresh: the prologue alone (decision k-1, s_c, marks, record,
+                                             // progress word) — no row is touched, no partial sums are left: cauchy_reform_kernel follows
 };
 
 __global__ __launch_bounds__(CA_T) void cauchy_fused_kernel(CauchyFusedArgs a) {
@@ -648,7 +658,7 @@ __global__ __launch_bounds__(CA_T) void cauchy_fused_kernel(CauchyFusedArgs a) {
             __hip_atomic_store(a.mirror, wv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
-    if (done) return;
+    if (done || a.decide_only) return;
     // ---- this workgroup's rows: t_s += theta t_d, t_d -= d_ind J~[:, ind], and the partial sums for the next decision -------------
     double acc[2] = {0.0, 0.0};
     for (int64_t i = r0; i < a.nrows; i += (int64_t)gridDim.x * CA_T) {
@@ -663,6 +673,152 @@ __global__ __launch_bounds__(CA_T) void cauchy_fused_kernel(CauchyFusedArgs a) {
     }
     block_reduce<CA_T, 2>(acc, rscratch, OpSum(), 0.0);
     if (tid == 0) { a.part_out[blockIdx.x] = acc[0]; a.part_out[gridDim.x + blockIdx.x] = acc[1]; }
+}
+
+// Option cauchy_image_refresh, one-kernel-per-breakpoint form: t_d = J~ d and t_s = J~ s_c formed AGAIN from J at launch k (every
+// R-th), behind a decide_only launch of cauchy_fused_kernel, so that the rounding of up to R - 1 rank-one updates does not stay in the
+// images while ||d|| shrinks by orders of magnitude (the reference forms a fresh H*d at every breakpoint, :633).
+// One sweep over the row-major image with TWO right-hand sides, on the row-stream machinery of bh_matvec.hip.h: a workgroup owns
+// row groups blockIdx.x, +gridDim.x, ...; T threads x CPT 16-byte non-temporal loads per row, R rows per step, the next group's loads
+// issued before the current group's reduction; each row of J is read once and both products are taken from the registers that hold
+// it.  d is not stored in this form: d_i = 0 when fixpass[i] <= k (fixed by launch k or earlier), -g_i otherwise; s_c = sbuf[k & 1],
+// written by the launch before.  Both per-row sums have a fixed order (chunk order per lane, wave butterfly, waves ascending): a
+// repeated search is bit-identical.  No atomics; nothing this launch writes (t_d, t_s, part) is read by it.
+// VL = 1 (8192 < n <= 16384): two row buffers and two vector slices do not fit 256 VGPRs, so each lane parks its slice of d in LDS
+// (dynamic, T x CPT x 16 bytes, lane-private slots: no barrier) as row_stream_kernel's fused mode does with v.
+struct CauchyReformArgs {
+    const CauchyPass* gate;                  // pp[k & 1], written by the decide_only launch before: done -> nothing to form
+    int k;
+    const double* g; const int* fixpass; int n;
+    const double* s;                         // s_c: ld doubles of the library's own (16-byte aligned; entries from n on are ignored)
+    const double* J; int64_t ld; int64_t nrows, d_rows; double mu; int nchunks;
+    double* td; double* ts;
+    double* part;                            // [2][gridDim.x]: partial sums of w t_s t_d and of w t_d^2 for launch k + 1
+};
+
+template <int T, int CPT, int R, int VL>
+__global__ __launch_bounds__(T) void cauchy_reform_kernel(CauchyReformArgs a) {
+    // (a re-formation enqueued behind the end of the loop: launch k + 1 reads the record of the decide_only launch itself, pp[k & 1],
+    // so there is nothing to hand on here — and no load of J is issued)
+    if (a.gate->done) return;
+    constexpr int NW = T / 64;
+    __shared__ double red[2][2][R][NW];
+    extern __shared__ __attribute__((aligned(16))) double2 d_lds[];     // VL only: [CPT][T]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t ld2 = a.ld >> 1;
+    const double2* __restrict__ J2 = reinterpret_cast<const double2*>(a.J);
+    const int64_t ngroups = (a.nrows + R - 1) / R;
+    const int64_t G = gridDim.x;
+
+    bool act[CPT];
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) act[c] = (tid + c * T) < a.nchunks;
+    double2 A[R][CPT], B[R][CPT];
+    auto load_group = [&](double2 (&dst)[R][CPT], int64_t grp) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int64_t row = grp * R + r;
+            const bool rv = row < a.nrows;
+            const double2* rp = J2 + (rv ? row : 0) * ld2;
+#pragma unroll
+            for (int c = 0; c < CPT; ++c) {
+                dst[r][c] = make_double2(0.0, 0.0);
+                if (rv && act[c]) {
+                    const dvec2 t = __builtin_nontemporal_load(reinterpret_cast<const dvec2*>(rp + tid + c * T));
+                    dst[r][c] = make_double2(t.x, t.y);
+                }
+            }
+        }
+    };
+    int64_t g = blockIdx.x;
+    if (g < ngroups) load_group(A, g);                                   // the first row group does not depend on the vectors
+    // this lane's slices of d and s_c (g and the marks are read element by element: a device caller's g lies where it lies)
+    double2 vd[CPT], vs[CPT];
+    int2 fp[CPT];
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) {
+        const int i0 = 2 * (tid + c * T), i1 = i0 + 1;
+        vd[c] = vs[c] = make_double2(0.0, 0.0);
+        fp[c] = make_int2(-1, -1);
+        if (act[c]) vs[c] = reinterpret_cast<const double2*>(a.s)[tid + c * T];
+        if (i0 < a.n) { vd[c].x = a.g[i0]; fp[c].x = a.fixpass[i0]; }
+        if (i1 < a.n) { vd[c].y = a.g[i1]; fp[c].y = a.fixpass[i1]; }
+    }
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) {
+        const int i0 = 2 * (tid + c * T), i1 = i0 + 1;
+        vd[c].x = (i0 >= a.n || fp[c].x <= a.k) ? 0.0 : -vd[c].x;       // d = projection(lincons, -g), box constraints (:592 / :632)
+        vd[c].y = (i1 >= a.n || fp[c].y <= a.k) ? 0.0 : -vd[c].y;
+        if (i0 >= a.n) vs[c].x = 0.0;
+        if (i1 >= a.n) vs[c].y = 0.0;
+        if (VL) d_lds[c * T + tid] = vd[c];                              // read back only by this lane
+    }
+    double acc[2] = {0.0, 0.0};
+    int buf = 0;
+    auto process = [&](double2 (&X)[R][CPT], int64_t grp) {
+        double sd[R], ss[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            double ad = 0.0, as = 0.0;
+#pragma unroll
+            for (int c = 0; c < CPT; ++c) {
+                const double2 dk = VL ? d_lds[c * T + tid] : vd[c];
+                ad = fma(X[r][c].x, dk.x, ad);
+                ad = fma(X[r][c].y, dk.y, ad);
+                as = fma(X[r][c].x, vs[c].x, as);
+                as = fma(X[r][c].y, vs[c].y, as);
+            }
+            sd[r] = wave_sum(ad);
+            ss[r] = wave_sum(as);
+        }
+        if (NW > 1) {
+            if (lane == 0) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) { red[buf][0][r][wave] = sd[r]; red[buf][1][r][wave] = ss[r]; }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+                for (int w = 0; w < NW; ++w) { t0 += red[buf][0][r][w]; t1 += red[buf][1][r][w]; }
+                sd[r] = t0; ss[r] = t1;
+            }
+            buf ^= 1;
+        }
+        // the R results of the group leave in one store instruction per image (lanes 0..R-1 of wave 0)
+        double mine_d = 0.0, mine_s = 0.0;
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (tid == r) { mine_d = sd[r]; mine_s = ss[r]; }
+        const int64_t myrow = grp * R + tid;
+        if (tid < R && myrow < a.nrows) { a.td[myrow] = mine_d; a.ts[myrow] = mine_s; }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int64_t row = grp * R + r;
+            if (row < a.nrows) {
+                const double w = (row < a.d_rows) ? 1.0 : a.mu;
+                acc[0] = fma(w * ss[r], sd[r], acc[0]);
+                acc[1] = fma(w * sd[r], sd[r], acc[1]);
+            }
+        }
+    };
+    if (g < ngroups) {
+        while (true) {
+            int64_t gn = g + G;
+            if (gn < ngroups) load_group(B, gn);
+            process(A, g);
+            if (gn >= ngroups) break;
+            g = gn;
+            gn = g + G;
+            if (gn < ngroups) load_group(A, gn);
+            process(B, g);
+            if (gn >= ngroups) break;
+            g = gn;
+        }
+    }
+    // (every thread holds the same sums over this workgroup's rows, in ascending row order)
+    if (tid == 0) { a.part[blockIdx.x] = acc[0]; a.part[gridDim.x + blockIdx.x] = acc[1]; }
 }
 
 // M <- M - a a',  a = column `ind` of A (the variable that just became fixed):  A_free A_free' after add_active!.

@@ -488,7 +488,9 @@ def resid_sqnorm(rx):
 def set_option(key, value):
     """``bh_set_option``: process-wide integer options (the list with defaults is in include/benlsip_hip.h), e.g. ``cg_fused``,
     ``proj_form``, ``cauchy_image``, ``cauchy_gram``, ``cauchy_gram_eq`` (Cauchy search with 1..64 linear equalities from ``G`` on a
-    Gram-form handle, default 0) and ``gram_cg_fused`` (fused two- / three-kernel CG iteration on a Gram-form handle, default 0)."""
+    Gram-form handle, default 0), ``gram_cg_fused`` (fused two- / three-kernel CG iteration on a Gram-form handle, default 0) and
+    ``cauchy_image_refresh`` (row-space Cauchy search on one rank: R >= 1 forms the carried images again from ``J`` every R-th pass,
+    default 0 = never)."""
     check(_lib.lib().bh_set_option(key.encode(), int(value)), "bh_set_option(%s)" % key)
 
 

@@ -389,6 +389,20 @@ int32_t bh_stats_reset(bh_hess* H);
  *                        previous search on the same bh_proj took more than 4 (1 + mA) passes
  *   "cauchy_fused"   [1] that search (box constraints, one rank) with ONE kernel per breakpoint: every workgroup of the row kernel redoes the
  *                        previous pass's decision in its prologue (s_c and the loop state are ping-pong buffers); 0: two kernels per pass
+ *   "cauchy_image_refresh" [0] that row-space search ("cauchy_image", with or without equalities) on one rank: R >= 1 forms the carried images
+ *                        again from J and the device-side state at every pass index that is a positive multiple of R (the reference forms
+ *                        a fresh H*d at every breakpoint; the carried J d keeps an absolute error of k eps ||J d_0|| while ||d|| shrinks
+ *                        by orders of magnitude).  0 = never: every path, launch, counter and bit is what it is without the option.
+ *                        "cauchy_fused" = 1: a decision-only launch of cauchy_fused_kernel + cauchy_reform_kernel (J d and J s_c in ONE
+ *                        sweep, two right-hand sides; n <= 16384 — a wider J keeps its carried images); "cauchy_fused" = 0: two gated
+ *                        J v sweeps; with equalities: a (J v), B (the GEMM of "cauchy_gemm", else mA sweeps) and J s_c (J v).
+ *                        Not a change of the search: same decisions rule, same passes; a fresh product is rounded differently from the
+ *                        carried one, hence opt-in.  Re-formations enqueued behind the end of the loop are gated off and not counted:
+ *                        with m = floor((passes - 1) / R), stats.n_jv of a search grows by 1 + m ("cauchy_fused" = 1), 1 + 2 m
+ *                        ("cauchy_fused" = 0), with equalities 1 + 2 m ("cauchy_gemm" = 1) or 1 + mA + (2 + mA) m; n_hmul of the call
+ *                        (the passes) and n_breakpoints keep their meaning, bh_cauchy_info's form too (its launch count includes the
+ *                        extra launches).  Several ranks: ignored, the path is exactly the one without the option.
+ *                        A negative value: BH_ERR_INVALID_ARG
  *   "cauchy_gram"    [0] bh_cauchy_step(_dev) on a handle in the Gram form (bh_hess_set_form), no linear equalities, one rank: the whole
  *                        search in ONE launch from G (init -> G d -> cauchy_gram_kernel: Hd downdated by one row of G per breakpoint, the
  *                        loop runs on the device; the launch count does not depend on the number of breakpoints).  Any other handle or
