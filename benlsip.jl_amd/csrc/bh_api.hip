@@ -2,6 +2,7 @@
 // One process drives one GPU; all launches go to one stream; exports that move host data are synchronous, device-pointer
 // exports return once the host has what it is owed (option final_sync).
 #include "../../include/benlsip_hip.h"
+#include "bh_cauchy_plan.h"
 #include "bh_kernels.hip.h"
 
 #include <dlfcn.h>
@@ -18,9 +19,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <array>
 #include <initializer_list>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 using namespace bh;
@@ -237,16 +240,32 @@ void dev_free(void* p) { if (p) (void)hipFree(p); }
 // ------------------------------------------------------------------------------------------
 struct RsConfig { int T, CPT, R, blocks_per_cu; };
 
-// index -> template instantiation (see launch_row_stream)
-const RsConfig kRsConfigs[] = {
-    {64, 1, 8, 8},     // 0: nchunks <= 64    (n <= 128)
-    {256, 1, 8, 4},    // 1: nchunks <= 256   (n <= 512)
-    {256, 2, 8, 2},    // 2: nchunks <= 512   (n <= 1024)   2 WGs/CU measured best (6.5 vs 6.0 TB/s at 4)
-    {256, 4, 4, 2},    // 3: nchunks <= 1024  (n <= 2048)   2 WGs/CU measured best (6.6 vs 6.0 TB/s at 4)
-    {256, 8, 4, 1},    // 4: nchunks <= 2048  (n <= 4096)   measured best of nine geometries: 1 WG/CU, 128 KiB in flight
-    {512, 8, 2, 1},    // 5: nchunks <= 4096  (n <= 8192)
-    {512, 16, 1, 1},   // 6: nchunks <= 8192  (n <= 16384): one row per step; the fused mode parks v in LDS (VL)
+// One geometry as a type: T threads, CPT 16-byte chunks of the vector per thread, R rows per step; blocks_per_cu is its default grid.
+template <int T_, int CPT_, int R_, int BPC_>
+struct RsGeom {
+    static constexpr int T = T_, CPT = CPT_, R = R_, blocks_per_cu = BPC_;
+    static constexpr size_t vec_bytes = (size_t)T_ * CPT_ * sizeof(double2);   // one workgroup's slice of a vector
+    // n <= 16384 (the last geometry): a kernel that needs a second vector slice next to the row buffers parks it in LDS (VL = 1:
+    // T * CPT * 16 bytes = 128 KiB, above the 64 KiB a kernel may use without asking); the others keep everything in registers
+    static constexpr bool vec_in_lds = vec_bytes > 64 * 1024;
 };
+
+// index -> geometry.  The only place the triples are written: kRsConfigs and every launcher (with_rs_geom) take them from here.
+using RsGeoms = std::tuple<
+    RsGeom<64, 1, 8, 8>,     // 0: nchunks <= 64    (n <= 128)
+    RsGeom<256, 1, 8, 4>,    // 1: nchunks <= 256   (n <= 512)
+    RsGeom<256, 2, 8, 2>,    // 2: nchunks <= 512   (n <= 1024)   2 WGs/CU measured best (6.5 vs 6.0 TB/s at 4)
+    RsGeom<256, 4, 4, 2>,    // 3: nchunks <= 1024  (n <= 2048)   2 WGs/CU measured best (6.6 vs 6.0 TB/s at 4)
+    RsGeom<256, 8, 4, 1>,    // 4: nchunks <= 2048  (n <= 4096)   measured best of nine geometries: 1 WG/CU, 128 KiB in flight
+    RsGeom<512, 8, 2, 1>,    // 5: nchunks <= 4096  (n <= 8192)
+    RsGeom<512, 16, 1, 1>    // 6: nchunks <= 8192  (n <= 16384): one row per step; the fused mode parks v in LDS (VL)
+    >;
+constexpr int kNumRsConfigs = (int)std::tuple_size<RsGeoms>::value;
+static_assert(kNumRsConfigs == 7, "with_rs_geom and pick_config enumerate seven geometries");
+
+template <class... G>
+constexpr std::array<RsConfig, sizeof...(G)> rs_config_table(std::tuple<G...>) { return {{RsConfig{G::T, G::CPT, G::R, G::blocks_per_cu}...}}; }
+constexpr auto kRsConfigs = rs_config_table(RsGeoms{});
 constexpr int64_t kMaxChunks = 8192;
 constexpr int64_t kMaxBlocksPerCu = 8;   // partial-slab capacity per handle: n_cu * kMaxBlocksPerCu workgroups (alloc_hess_common)
 
@@ -260,8 +279,31 @@ int pick_config(int nchunks) {
     return 6;
 }
 
-template <int T, int CPT, int R>
+// The only switch over a geometry index: f(RsGeom<...>{}) for the geometry of `cfg`.  f is instantiated for all seven; what exists
+// for some of them only sits behind `if constexpr` in f.
+template <class F>
+void with_rs_geom(int cfg, F&& f) {
+    switch (cfg) {
+        case 0: f(std::tuple_element_t<0, RsGeoms>{}); break;
+        case 1: f(std::tuple_element_t<1, RsGeoms>{}); break;
+        case 2: f(std::tuple_element_t<2, RsGeoms>{}); break;
+        case 3: f(std::tuple_element_t<3, RsGeoms>{}); break;
+        case 4: f(std::tuple_element_t<4, RsGeoms>{}); break;
+        case 5: f(std::tuple_element_t<5, RsGeoms>{}); break;
+        default: f(std::tuple_element_t<6, RsGeoms>{}); break;
+    }
+}
+
+// Raise the dynamic-LDS ceiling of the kernels that park a vector slice in LDS, once per device (`granted`: a flag of Ctx).
+void grant_lds_once(bool& granted, size_t lds, std::initializer_list<const void*> kernels) {
+    if (granted) return;
+    for (const void* k : kernels) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    granted = true;
+}
+
+template <class G>
 void launch_rs_mode(int mode, const RowStreamArgs& a, int grid, hipStream_t s) {
+    constexpr int T = G::T, CPT = G::CPT, R = G::R;
     switch (mode) {
         case MODE_JV: hipLaunchKernelGGL((row_stream_kernel<T, CPT, R, MODE_JV>), dim3(grid), dim3(T), 0, s, a); break;
         case MODE_JTV: hipLaunchKernelGGL((row_stream_kernel<T, CPT, R, MODE_JTV>), dim3(grid), dim3(T), 0, s, a); break;
@@ -269,117 +311,72 @@ void launch_rs_mode(int mode, const RowStreamArgs& a, int grid, hipStream_t s) {
     }
 }
 
-// MODE_FUSED with the CG prologue (two-kernel box iteration).  CGP = 2: the launch expected to stop.
-template <int T, int CPT, int R>
-void launch_rs_cgp(const RowStreamArgs& a, int grid, hipStream_t s, bool expect_stop) {
-    if (expect_stop) hipLaunchKernelGGL((row_stream_kernel<T, CPT, R, MODE_FUSED, 1, 1, 0, 2>), dim3(grid), dim3(T), 0, s, a);
-    else hipLaunchKernelGGL((row_stream_kernel<T, CPT, R, MODE_FUSED, 1, 1, 0, 1>), dim3(grid), dim3(T), 0, s, a);
-}
-
-// n <= 16384: J v and J'u keep everything in registers; the fused mode needs the v slice in LDS (T * CPT * 16 bytes = 128 KiB,
-// above the 64 KiB a kernel may use without asking).
-template <int T, int CPT, int R>
-void launch_rs_mode_vlds(int mode, const RowStreamArgs& a, int grid, hipStream_t s) {
-    if (mode != MODE_FUSED) { launch_rs_mode<T, CPT, R>(mode, a, grid, s); return; }
-    constexpr size_t lds = (size_t)T * CPT * sizeof(double2);
-    if (!g_ctx.vlds_attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&row_stream_kernel<T, CPT, R, MODE_FUSED, 1, 1, 1>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        g_ctx.vlds_attr_set = true;
-    }
-    hipLaunchKernelGGL((row_stream_kernel<T, CPT, R, MODE_FUSED, 1, 1, 1>), dim3(grid), dim3(T), lds, s, a);
-}
-
+// J v and J'u keep everything in registers in every geometry; the fused mode of a vec_in_lds geometry needs the v slice in LDS.
 void launch_row_stream(int cfg, int mode, const RowStreamArgs& a, int grid, hipStream_t s) {
-    switch (cfg) {
-        case 0: launch_rs_mode<64, 1, 8>(mode, a, grid, s); break;
-        case 1: launch_rs_mode<256, 1, 8>(mode, a, grid, s); break;
-        case 2: launch_rs_mode<256, 2, 8>(mode, a, grid, s); break;
-        case 3: launch_rs_mode<256, 4, 4>(mode, a, grid, s); break;
-        case 4: launch_rs_mode<256, 8, 4>(mode, a, grid, s); break;
-        case 5: launch_rs_mode<512, 8, 2>(mode, a, grid, s); break;
-        default: launch_rs_mode_vlds<512, 16, 1>(mode, a, grid, s); break;
-    }
+    with_rs_geom(cfg, [&](auto geom) {
+        using G = decltype(geom);
+        if constexpr (G::vec_in_lds) {
+            if (mode == MODE_FUSED) {
+                auto* kernel = &row_stream_kernel<G::T, G::CPT, G::R, MODE_FUSED, 1, 1, 1>;
+                grant_lds_once(g_ctx.vlds_attr_set, G::vec_bytes, {reinterpret_cast<const void*>(kernel)});
+                hipLaunchKernelGGL(kernel, dim3(grid), dim3(G::T), G::vec_bytes, s, a);
+                return;
+            }
+        }
+        launch_rs_mode<G>(mode, a, grid, s);
+    });
 }
 
 // CGP = 3: the RCCL form (update of the previous iteration folded into the prologue); register-resident geometries only.
-bool cgp3_supported(int cfg) { return cfg <= 5; }
+bool cgp3_supported(int cfg) {
+    bool ok = false;
+    with_rs_geom(cfg, [&](auto geom) { ok = !decltype(geom)::vec_in_lds; });
+    return ok;
+}
 void launch_row_stream_cgp3(int cfg, const RowStreamArgs& a, int grid, hipStream_t s) {
-    switch (cfg) {
-        case 0: hipLaunchKernelGGL((row_stream_kernel<64, 1, 8, MODE_FUSED, 1, 1, 0, 3>), dim3(grid), dim3(64), 0, s, a); break;
-        case 1: hipLaunchKernelGGL((row_stream_kernel<256, 1, 8, MODE_FUSED, 1, 1, 0, 3>), dim3(grid), dim3(256), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((row_stream_kernel<256, 2, 8, MODE_FUSED, 1, 1, 0, 3>), dim3(grid), dim3(256), 0, s, a); break;
-        case 3: hipLaunchKernelGGL((row_stream_kernel<256, 4, 4, MODE_FUSED, 1, 1, 0, 3>), dim3(grid), dim3(256), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((row_stream_kernel<256, 8, 4, MODE_FUSED, 1, 1, 0, 3>), dim3(grid), dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL((row_stream_kernel<512, 8, 2, MODE_FUSED, 1, 1, 0, 3>), dim3(grid), dim3(512), 0, s, a); break;
-    }
+    with_rs_geom(cfg, [&](auto geom) {
+        using G = decltype(geom);
+        if constexpr (!G::vec_in_lds)
+            hipLaunchKernelGGL((row_stream_kernel<G::T, G::CPT, G::R, MODE_FUSED, 1, 1, 0, 3>), dim3(grid), dim3(G::T), 0, s, a);
+    });
 }
 
+// MODE_FUSED with the CG prologue (two-kernel box iteration).  CGP = 2: the launch expected to stop.
 void launch_row_stream_cgp(int cfg, const RowStreamArgs& a, int grid, hipStream_t s, bool expect_stop) {
-    switch (cfg) {
-        case 0: launch_rs_cgp<64, 1, 8>(a, grid, s, expect_stop); break;
-        case 1: launch_rs_cgp<256, 1, 8>(a, grid, s, expect_stop); break;
-        case 2: launch_rs_cgp<256, 2, 8>(a, grid, s, expect_stop); break;
-        case 3: launch_rs_cgp<256, 4, 4>(a, grid, s, expect_stop); break;
-        case 4: launch_rs_cgp<256, 8, 4>(a, grid, s, expect_stop); break;
-        case 5: launch_rs_cgp<512, 8, 2>(a, grid, s, expect_stop); break;
-        default: {
-            constexpr size_t lds = (size_t)512 * 16 * sizeof(double2);
-            if (!g_ctx.cgp_vlds_attr_set) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&row_stream_kernel<512, 16, 1, MODE_FUSED, 1, 1, 1, 1>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&row_stream_kernel<512, 16, 1, MODE_FUSED, 1, 1, 1, 2>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                g_ctx.cgp_vlds_attr_set = true;
-            }
-            if (expect_stop) hipLaunchKernelGGL((row_stream_kernel<512, 16, 1, MODE_FUSED, 1, 1, 1, 2>), dim3(grid), dim3(512), lds, s, a);
-            else hipLaunchKernelGGL((row_stream_kernel<512, 16, 1, MODE_FUSED, 1, 1, 1, 1>), dim3(grid), dim3(512), lds, s, a);
-            break;
-        }
-    }
+    with_rs_geom(cfg, [&](auto geom) {
+        using G = decltype(geom);
+        constexpr int VL = G::vec_in_lds ? 1 : 0;
+        constexpr size_t lds = VL ? G::vec_bytes : 0;
+        auto* go_on = &row_stream_kernel<G::T, G::CPT, G::R, MODE_FUSED, 1, 1, VL, 1>;
+        auto* stop = &row_stream_kernel<G::T, G::CPT, G::R, MODE_FUSED, 1, 1, VL, 2>;
+        if constexpr (VL != 0)
+            grant_lds_once(g_ctx.cgp_vlds_attr_set, lds, {reinterpret_cast<const void*>(go_on), reinterpret_cast<const void*>(stop)});
+        if (expect_stop) hipLaunchKernelGGL(stop, dim3(grid), dim3(G::T), lds, s, a);
+        else hipLaunchKernelGGL(go_on, dim3(grid), dim3(G::T), lds, s, a);
+    });
 }
 
 // Option cauchy_image_refresh, one-kernel-per-breakpoint form: t_d = J~ d, t_s = J~ s_c and their sums in one sweep (cauchy_reform_kernel),
-// the geometries of kRsConfigs.  n <= 8192: both vector slices in registers; above, the slice of d in LDS (128 KiB, asked for once).
+// every geometry.  n <= 8192: both vector slices in registers; above, the slice of d in LDS (128 KiB, asked for once).
 void launch_cauchy_reform(int cfg, const CauchyReformArgs& a, int grid, hipStream_t s) {
-    switch (cfg) {
-        case 0: hipLaunchKernelGGL((cauchy_reform_kernel<64, 1, 8, 0>), dim3(grid), dim3(64), 0, s, a); break;
-        case 1: hipLaunchKernelGGL((cauchy_reform_kernel<256, 1, 8, 0>), dim3(grid), dim3(256), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((cauchy_reform_kernel<256, 2, 8, 0>), dim3(grid), dim3(256), 0, s, a); break;
-        case 3: hipLaunchKernelGGL((cauchy_reform_kernel<256, 4, 4, 0>), dim3(grid), dim3(256), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((cauchy_reform_kernel<256, 8, 4, 0>), dim3(grid), dim3(256), 0, s, a); break;
-        case 5: hipLaunchKernelGGL((cauchy_reform_kernel<512, 8, 2, 0>), dim3(grid), dim3(512), 0, s, a); break;
-        default: {
-            constexpr size_t lds = (size_t)512 * 16 * sizeof(double2);
-            if (!g_ctx.reform_vlds_attr_set) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cauchy_reform_kernel<512, 16, 1, 1>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                g_ctx.reform_vlds_attr_set = true;
-            }
-            hipLaunchKernelGGL((cauchy_reform_kernel<512, 16, 1, 1>), dim3(grid), dim3(512), lds, s, a);
-            break;
-        }
-    }
+    with_rs_geom(cfg, [&](auto geom) {
+        using G = decltype(geom);
+        constexpr int VL = G::vec_in_lds ? 1 : 0;
+        constexpr size_t lds = VL ? G::vec_bytes : 0;
+        auto* kernel = &cauchy_reform_kernel<G::T, G::CPT, G::R, VL>;
+        if constexpr (VL != 0) grant_lds_once(g_ctx.reform_vlds_attr_set, lds, {reinterpret_cast<const void*>(kernel)});
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(G::T), lds, s, a);
+    });
 }
 
-// Gram form, option gram_cg_fused: G·v with the CG prologue (bh_gramcg.hip.h), the geometries of kRsConfigs over the ld rows of G.
+// Gram form, option gram_cg_fused: G·v with the CG prologue (bh_gramcg.hip.h), every geometry over the ld rows of G.
 // Every instantiation holds its slice of p and both row buffers in registers (no z accumulators: nothing is parked in LDS).
-template <int T, int CPT, int R>
-void launch_gram_cg_geom(const RowStreamArgs& a, int grid, hipStream_t s, bool expect_stop) {
-    if (expect_stop) hipLaunchKernelGGL((gram_cg_kernel<T, CPT, R, 1>), dim3(grid), dim3(T), 0, s, a);
-    else hipLaunchKernelGGL((gram_cg_kernel<T, CPT, R, 0>), dim3(grid), dim3(T), 0, s, a);
-}
-
 void launch_gram_cg(int cfg, const RowStreamArgs& a, int grid, hipStream_t s, bool expect_stop) {
-    switch (cfg) {
-        case 0: launch_gram_cg_geom<64, 1, 8>(a, grid, s, expect_stop); break;
-        case 1: launch_gram_cg_geom<256, 1, 8>(a, grid, s, expect_stop); break;
-        case 2: launch_gram_cg_geom<256, 2, 8>(a, grid, s, expect_stop); break;
-        case 3: launch_gram_cg_geom<256, 4, 4>(a, grid, s, expect_stop); break;
-        case 4: launch_gram_cg_geom<256, 8, 4>(a, grid, s, expect_stop); break;
-        case 5: launch_gram_cg_geom<512, 8, 2>(a, grid, s, expect_stop); break;
-        default: launch_gram_cg_geom<512, 16, 1>(a, grid, s, expect_stop); break;
-    }
+    with_rs_geom(cfg, [&](auto geom) {
+        using G = decltype(geom);
+        if (expect_stop) hipLaunchKernelGGL((gram_cg_kernel<G::T, G::CPT, G::R, 1>), dim3(grid), dim3(G::T), 0, s, a);
+        else hipLaunchKernelGGL((gram_cg_kernel<G::T, G::CPT, G::R, 0>), dim3(grid), dim3(G::T), 0, s, a);
+    });
 }
 
 int grid_for(int cfg, int64_t nrows) {
@@ -3152,10 +3149,339 @@ static int32_t adopt_device_mask(bh_proj* P, uint64_t* fix_chunks_out, int* info
     return BH_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// cauchy_step: the plan of one search (decided once), its run context, one launcher per form
+// ------------------------------------------------------------------------------------------
+struct CauchyPlan {
+    CauchyForm form = CAUCHY_SWEEP; bool fused = false; int refresh = 0;   // the selection (bh_cauchy_plan.h)
+    bool gemm = false;              // row space with equalities: B = J~ D A' by image_b_mfma_kernel (else mA J v sweeps)
+    bool gen_tiled = false;         // ... and its row body in tiles of 64 rows (few equalities: one row per thread, see bh_cauchy.hip.h)
+    bool factor_downdate = false;   // sweeping form: rank-one downdates of the factor itself
+    int img_grid = 1, fused_grid = 1, gen_grid = 1, reform_cfg = 0, reform_grid = 1;
+    int part_G = 1;                 // how many partial sums a row kernel leaves
+    int off = 0, batch = 1, max_pass = 1;   // the launch-ahead schedule (off: see cauchy_impl)
+    bool image() const { return form == CAUCHY_ROWSPACE_BOX || form == CAUCHY_ROWSPACE_EQ; }
+    bool reforms_at(int index) const { return refresh > 0 && index > 0 && (index % refresh) == 0; }
+};
+
+// What the passes of one search share.
+struct CauchyRun {
+    bh_hess* H;
+    bh_proj* P;
+    CgWorkspace& c;
+    hipStream_t s;
+    CauchyArgs a{};
+    CauchyPlan plan;
+    int64_t img_rows = 0;           // rows of J~ = [J; C] on this rank
+    int64_t img_cap = 0;            // ... as the images are laid out: rounded up to even (16-byte aligned tails)
+    double* img_scal = nullptr;
+    CauchyPass* pp = nullptr;
+    double* part_pp[2] = {nullptr, nullptr};
+    double* sbuf[2] = {nullptr, nullptr};   // s_c ping-pong of the fused form (H*d is never formed there)
+    int reform_sweeps = 0;          // sweeps over J of one re-formation, for stats.n_jv
+};
+
+// Decides everything about the search from the handles and the options.  Launches and allocates nothing.
+static CauchyPlan cauchy_make_plan(const bh_hess* H, const bh_proj* P) {
+    const int mA = (int)P->mA;
+    CauchySelectIn in{};
+    in.gram_handle = H->form == BH_HESS_GRAM; in.mA = mA; in.comm = comm_active(); in.lda_is_ld = P->ldA == H->ld;
+    in.multi_panel = multi_panel(H); in.last_cauchy_passes = P->last_cauchy_passes;
+    in.cauchy_image = g_ctx.opt_cauchy_image; in.cauchy_image_max_ma = g_ctx.opt_cauchy_image_max_ma; in.cauchy_fused = g_ctx.opt_cauchy_fused;
+    in.cauchy_gram = g_ctx.opt_cauchy_gram; in.cauchy_gram_eq = g_ctx.opt_cauchy_gram_eq; in.cauchy_image_refresh = g_ctx.opt_cauchy_image_refresh;
+    const CauchySelection sel = cauchy_select(in);
+    CauchyPlan p;
+    p.form = sel.form; p.fused = sel.fused; p.refresh = sel.refresh;
+    // B = J~ D A' (rows x mA): ONE sweep on the matrix cores (image_b_mfma_kernel) when the images share their leading dimension,
+    // else mA J v sweeps over masked rows of A
+    p.gemm = g_ctx.opt_cauchy_gemm != 0 && P->ldA == H->ld;
+    p.gen_tiled = mA > 16;
+    // chol_downdate = 1 only has a case where refactoring is expensive (mA > 64: blocked factorisation, 0.21 ms at mA = 256);
+    // up to 64 rows the register-panel Cholesky (18.5 us) costs what the rank-one downdate costs (20 us), so the factor is
+    // always rebuilt from the downdated Gram matrix there — as accurate as the reference's from-scratch rebuild.
+    p.factor_downdate = g_ctx.opt_chol_downdate && mA > 64;
+    const int64_t img_rows = H->d + H->q_eff;
+    p.reform_cfg = pick_config(std::min<int>(H->nchunks, (int)kMaxChunks));
+    p.reform_grid = std::min(kCauchyFusedGrid, grid_for(p.reform_cfg, img_rows));
+    p.img_grid = (int)std::max<int64_t>(1, std::min<int64_t>(p.fused ? kCauchyFusedGrid : kCauchyImgGrid, (img_rows + 255) / 256));
+    // (fewer, fatter workgroups measured slower: docs/design_history_r3.md)
+    p.fused_grid = (int)std::max<int64_t>(1, std::min<int64_t>(kCauchyFusedGrid, (img_rows + CA_T - 1) / CA_T));
+    // with equalities a workgroup takes tiles of 64 rows; the partial sums still have to fit the [2][kCauchyImgGrid] slot
+    p.gen_grid = (int)std::max<int64_t>(1, std::min<int64_t>(kCauchyImgGrid, (img_rows + 63) / 64));
+    p.part_G = (p.form == CAUCHY_ROWSPACE_EQ && p.gen_tiled) ? p.gen_grid : p.img_grid;
+    p.max_pass = (int)(H->n + 1);
+    // image-space passes take ~17 us: keep a deeper queue ahead of the GPU (over RCCL every over-launched pass costs a collective)
+    p.batch = (!p.image() && p.form != CAUCHY_GRAM_EQ) ? launch_batch_size(H) : (comm_active() && !use_peer_path()) ? 4 : 8;
+    p.off = p.fused ? 1 : 0;
+    return p;
+}
+
+// The buffers of the chosen form, grown before the first launch: the images t_d, t_s (+ partial sums and a 16-double tail), a and B
+// of the row-space form with equalities, a and B of the Gram form with equalities.
+static int32_t cauchy_ensure_buffers(CauchyRun& r) {
+    bh_hess* H = r.H;
+    const int mA = (int)r.P->mA;
+    const int64_t img_cap = r.img_cap;
+    if (r.plan.image()) {
+        BH_TRY(hess_ready(H));
+        if (!H->timg) BH_TRY(dev_alloc(&H->timg, 2 * img_cap + 2 * kCauchyImgGrid + 16));
+        r.img_scal = H->timg + 2 * img_cap + 2 * kCauchyImgGrid;
+        r.a.img_part = comm_active() ? r.img_scal : H->timg + 2 * img_cap;
+        r.a.img_G = comm_active() ? 1 : r.plan.part_G;
+        if (r.plan.form == CAUCHY_ROWSPACE_EQ && H->timg_gen_doubles < (int64_t)(1 + mA) * img_cap) {
+            dev_free(H->timg_gen);
+            H->timg_gen = nullptr; H->timg_gen_doubles = 0;
+            BH_TRY(dev_alloc(&H->timg_gen, (int64_t)(1 + mA) * img_cap));
+            H->timg_gen_doubles = (int64_t)(1 + mA) * img_cap;
+        }
+    }
+    if (r.plan.form == CAUCHY_GRAM_EQ && H->geq_doubles < (int64_t)(1 + mA) * H->ld) {
+        if (H->geq) BH_HIP(hipStreamSynchronize(r.s));            // (launches of an earlier search may still be queued)
+        dev_free(H->geq);
+        H->geq = nullptr; H->geq_doubles = 0;
+        BH_TRY(dev_alloc(&H->geq, (int64_t)(1 + mA) * H->ld));
+        H->geq_doubles = (int64_t)(1 + mA) * H->ld;
+    }
+    r.sbuf[0] = r.c.w; r.sbuf[1] = r.c.Hp;
+    if (r.plan.fused) {
+        r.pp = reinterpret_cast<CauchyPass*>(r.img_scal + 8);     // 2 x 32 bytes in the 16-double tail of timg
+        r.part_pp[0] = H->timg + 2 * img_cap; r.part_pp[1] = r.part_pp[0] + 2 * kCauchyFusedGrid;
+        r.a.fixpass = reinterpret_cast<int*>(r.c.v); r.a.pp0 = r.pp;
+    }
+    return BH_OK;
+}
+
+// What every launch of cauchy_image_kernel / the row body with equalities is told about the images (first, fresh: the caller's).
+static CauchyImgArgs cauchy_img_args(const CauchyRun& r) {
+    const bh_hess* H = r.H;
+    CauchyImgArgs ia{};
+    ia.st = r.c.d_state; ia.J = H->Jd; ia.ld = H->ld; ia.nrows = r.img_rows; ia.d_rows = H->d; ia.mu = H->mu;
+    ia.td = H->timg; ia.ts = H->timg + r.img_cap; ia.part = H->timg + 2 * r.img_cap;
+    return ia;
+}
+
+static int cauchy_mask_grid(int64_t n) { return std::max(1, std::min((int)((n + 255) / 256), 1024)); }
+
+// Factor of the current active set and y = (A_free A_free')^{-1} A_free(-g) (left in P->tw), as in the sweeping form:
+// [downdate + refactorisation + right-hand side + the two solves: y] in one launch behind a decision, two launches at pass 0.
+static int32_t cauchy_factor_solve(CauchyRun& r, const ProjArgs& pa, int index) {
+    bh_proj* P = r.P;
+    const int mA = (int)P->mA;
+    if (index > 0) {
+        P->linv_valid = false;
+        hipLaunchKernelGGL(cauchy_factor_solve_kernel, dim3(1), dim3(256), 0, r.s, P->M, P->Lr, mA, P->info, pa, (const double*)r.c.r,
+                           (const double*)P->tpart, (const CgState*)r.c.d_state);
+    } else {
+        hipLaunchKernelGGL(proj_left_mul_kernel, dim3(mA), dim3(256), 0, r.s, pa, (const double*)r.c.r);     // t (:86-98), then y
+        hipLaunchKernelGGL(trsv_small_kernel, dim3(1), dim3(256), 0, r.s, pa);
+    }
+    BH_HIP(hipGetLastError());
+    return BH_OK;
+}
+
+// Behind the row kernel of a two-kernel pass: the two sums over all ranks, then the single-workgroup decision.
+static int32_t cauchy_sum_and_advance(CauchyRun& r, const double* part) {
+    if (comm_active()) {
+        hipLaunchKernelGGL(cauchy_image_sum_kernel, dim3(1), dim3(64), 0, r.s, part, r.plan.part_G, r.img_scal, (const CgState*)r.c.d_state);
+        BH_TRY(allreduce_inplace(r.img_scal, 2, r.H, r.c.d_state));
+    }
+    hipLaunchKernelGGL(cauchy_advance_kernel, dim3(1), dim3(CA_T), 0, r.s, r.a);
+    BH_HIP(hipGetLastError());
+    return BH_OK;
+}
+
+// Form 0: per breakpoint the factor of the new active set, d = P(-g), one H*d sweep, the decision.
+static int32_t cauchy_pass_sweep(CauchyRun& r, int index) {
+    bh_hess* H = r.H; bh_proj* P = r.P; CgWorkspace& c = r.c; hipStream_t s = r.s;
+    const int mA = (int)P->mA;
+    if (index > 0 && mA > 0) {
+        if (r.plan.factor_downdate && (index % kDowndateRefresh) == 0) {
+            // every kDowndateRefresh-th breakpoint the factor is rebuilt from the device-side mask: hyperbolic downdates lose
+            // accuracy cumulatively, and without bound once A_free A_free' approaches singularity (c = sqrt(1 - s^2) -> 0)
+            BH_TRY(launch_reduced_factor(P, true, (const CgState*)c.d_state));
+        } else if (r.plan.factor_downdate) {
+            P->M_valid = false;     // only the factor follows the active set on this path
+            // add_active!: one more fixed variable = rank-one downdate of chol(A_free A_free'), O(mA^2)
+            P->linv_valid = false;
+            hipLaunchKernelGGL(chol_downdate_kernel, dim3(1), dim3(CG_T), (size_t)mA * sizeof(double), s, P->Lr, (const double*)P->Ad,
+                               P->ldA, mA, P->info, (const CgState*)c.d_state);
+        } else {
+            // refactor from the downdated Gram matrix, O(mA^3)
+            hipLaunchKernelGGL(gram_downdate_kernel, dim3(std::max(1, (mA * mA + 255) / 256)), dim3(256), 0, s, P->M, P->Ad, P->ldA, mA,
+                               (const CgState*)c.d_state);
+            BH_TRY(launch_chol(P, (const CgState*)c.d_state));
+        }
+    }
+    if (mA > 0) BH_TRY(launch_project(P, c.r, c.p, c.d_state, true));       // d = P(-g)   :592 / :632  (box: kept in place)
+    BH_TRY(launch_hmul(H, c.p, c.Hp, c.d_state, -1));           // Hd = H*d    :609 / :633
+    hipLaunchKernelGGL(cauchy_advance_kernel, dim3(1), dim3(CA_T), 0, s, r.a);
+    BH_HIP(hipGetLastError());
+    return BH_OK;
+}
+
+// Form 1, two kernels per breakpoint: cauchy_image_kernel over the rows, then the decision.
+static int32_t cauchy_pass_rowspace_box(CauchyRun& r, int index) {
+    bh_hess* H = r.H; CgWorkspace& c = r.c;
+    CauchyImgArgs ia = cauchy_img_args(r);
+    ia.first = index == 0 ? 1 : 0;
+    ia.fresh = r.plan.reforms_at(index) ? 1 : 0;
+    if (index == 0) {
+        BH_TRY(launch_jv(H, c.p, H->timg, true, nullptr));              // t_d = J~ d_0 (:609 in the row space)
+        H->stats.n_jv += 1;
+    }
+    if (ia.fresh) {
+        // t_d = J~ d from the d the advance kernel keeps (d[ind] is zero already), t_s = J~ s_c: gated by `done`
+        BH_TRY(launch_jv(H, c.p, H->timg, true, nullptr, (const CgState*)c.d_state));
+        BH_TRY(launch_jv(H, c.w, H->timg + r.img_cap, true, nullptr, (const CgState*)c.d_state));
+        r.reform_sweeps = 2;
+    }
+    hipLaunchKernelGGL(cauchy_image_kernel, dim3(r.plan.img_grid), dim3(256), 0, r.s, ia);
+    return cauchy_sum_and_advance(r, ia.part);
+}
+
+// Form 1, one kernel per breakpoint: launch 0 forms the images; launch k > 0 takes decision k-1 in the prologue of the row kernel of
+// pass k (cauchy_fused_kernel); a launch with a re-formation takes the decision alone and forms both images from J.
+static int32_t cauchy_pass_rowspace_fused(CauchyRun& r, int index) {
+    bh_hess* H = r.H; CgWorkspace& c = r.c; hipStream_t s = r.s;
+    const CauchyPlan& p = r.plan;
+    const CauchyArgs& a = r.a;
+    if (index == 0) {                                              // launch 0: t_d = J~ d_0 (:609 in the row space), t_s = 0, their sums
+        CauchyImgArgs ia = cauchy_img_args(r);
+        ia.first = 1;
+        BH_TRY(launch_jv(H, c.p, H->timg, true, nullptr));
+        H->stats.n_jv += 1;
+        hipLaunchKernelGGL(cauchy_image_kernel, dim3(p.img_grid), dim3(256), 0, s, ia);
+        BH_HIP(hipGetLastError());
+        return BH_OK;
+    }
+    CauchyFusedArgs fa{};
+    fa.pp = r.pp; fa.k = index; fa.g = a.g; fa.dl = a.dl; fa.du = a.du; fa.sbuf[0] = r.sbuf[0]; fa.sbuf[1] = r.sbuf[1];
+    fa.fixpass = a.fixpass; fa.fixrank = r.P->fixrank; fa.n = a.n; fa.nmm = a.nmm;
+    fa.J = H->Jd; fa.ld = H->ld; fa.nrows = r.img_rows; fa.d_rows = H->d; fa.mu = H->mu;
+    fa.td = H->timg; fa.ts = H->timg + r.img_cap;
+    fa.part_in = r.part_pp[(index - 1) & 1]; fa.Gin = index == 1 ? p.img_grid : p.reforms_at(index - 1) ? p.reform_grid : p.fused_grid;
+    fa.part_out = r.part_pp[index & 1];
+    fa.mirror = a.mirror; fa.tag = a.tag;
+    if (p.reforms_at(index)) {
+        // decision index-1 alone (every group of 64 elements of s_c has its owner at any grid), then both images from J
+        fa.decide_only = 1;
+        const int dec_grid = (int)std::max<int64_t>(1, std::min<int64_t>(p.fused_grid, ((int64_t)a.n + 63) / 64));
+        hipLaunchKernelGGL(cauchy_fused_kernel, dim3(dec_grid), dim3(CA_T), 0, s, fa);
+        CauchyReformArgs ra{};
+        ra.gate = r.pp + (index & 1); ra.k = index; ra.g = a.g; ra.fixpass = a.fixpass; ra.n = a.n; ra.s = r.sbuf[index & 1];
+        ra.J = H->Jd; ra.ld = H->ld; ra.nrows = r.img_rows; ra.d_rows = H->d; ra.mu = H->mu; ra.nchunks = H->nchunks;
+        ra.td = fa.td; ra.ts = fa.ts; ra.part = r.part_pp[index & 1];
+        launch_cauchy_reform(p.reform_cfg, ra, p.reform_grid, s);
+        r.reform_sweeps = 1;
+    } else {
+        hipLaunchKernelGGL(cauchy_fused_kernel, dim3(p.fused_grid), dim3(CA_T), 0, s, fa);
+    }
+    BH_HIP(hipGetLastError());
+    return BH_OK;
+}
+
+// Form 2.  Three launches per pass (mA <= 64): [downdate + refactorisation + right-hand side + the two solves: y]
+// -> [rows | d = P(-g) | t_fresh = A_free(-g) for the next pass] -> [decision]
+static int32_t cauchy_pass_rowspace_eq(CauchyRun& r, int index) {
+    bh_hess* H = r.H; bh_proj* P = r.P; CgWorkspace& c = r.c; hipStream_t s = r.s;
+    const CauchyPlan& p = r.plan;
+    const int mA = (int)P->mA;
+    const int64_t n = H->n, rows_cap = r.img_cap;
+    CauchyImgArgs ia = cauchy_img_args(r);
+    ia.first = index == 0 ? 1 : 0;
+    ia.fresh = p.reforms_at(index) ? 1 : 0;
+    ProjArgs pa = proj_args(P, c.d_state, true, true);
+    BH_TRY(cauchy_factor_solve(r, pa, index));
+    if (index == 0 || ia.fresh) {
+        // (index > 0: the re-formation of option cauchy_image_refresh, from the device-side mask — which holds the variable
+        // the decision of pass index-1 fixed — and gated by `done`; t_s = J~ s_c from the s_c that decision left)
+        const CgState* gate = index == 0 ? nullptr : (const CgState*)c.d_state;
+        // a = J~ D g: one J v sweep over the masked g.  B = J~ D A' (rows x mA): the GEMM, or mA J v sweeps (CauchyPlan::gemm)
+        const int mgrid = cauchy_mask_grid(n);
+        for (int j = -1; j < (p.gemm ? 0 : mA); ++j) {
+            const double* src = (j < 0) ? r.a.g : (const double*)(P->Ad + (int64_t)j * P->ldA);
+            hipLaunchKernelGGL(proj_mask_kernel, dim3(mgrid), dim3(256), 0, s, src, H->vpad, (const int*)P->fixrank, (int)n, gate);
+            BH_TRY(launch_jv(H, H->vpad, H->timg_gen + (int64_t)(j + 1) * rows_cap, true, nullptr, gate));
+            if (index == 0) H->stats.n_jv += 1;
+        }
+        if (p.gemm && r.img_rows > 0) {                 // (a rank without rows has no rows of B)
+            hipLaunchKernelGGL(image_b_mfma_kernel, dim3((unsigned)((r.img_rows + 127) / 128)), dim3(256), 0, s, (const double*)H->Jd, H->ld,
+                               r.img_rows, (const double*)P->Ad, P->ldA, mA, (const int*)P->fixrank, H->timg_gen + rows_cap, rows_cap, gate);
+            BH_HIP(hipGetLastError());
+        }
+        if (index > 0) {
+            BH_TRY(launch_jv(H, c.w, H->timg + rows_cap, true, nullptr, gate));
+            r.reform_sweeps = (p.gemm ? 1 : 1 + mA) + 1;
+        }
+    }
+    CauchyImgGenArgs ga{};
+    ga.b = ia; ga.a = H->timg_gen; ga.B = H->timg_gen + rows_cap; ga.rows_cap = rows_cap; ga.mA = mA;
+    ga.A = P->Ad; ga.ldA = P->ldA; ga.tw = P->tw; ga.g = r.a.g;
+    const int dblocks = ((int)(n + 1) / 2 + 63) / 64;
+    hipLaunchKernelGGL(cauchy_gen_rows_and_d_kernel, dim3(p.part_G + dblocks + mA), dim3(256), 0, s, ga, p.gen_tiled ? 1 : 0, p.part_G, dblocks, pa,
+                       (const double*)c.r, c.p, P->tpart);
+    return cauchy_sum_and_advance(r, ia.part);
+}
+
+// Form 4: per pass [factor + solves: y] -> [Hd = -a - B y | d = P(-g) | t_fresh] -> [decision from Hd].
+static int32_t cauchy_pass_gram_eq(CauchyRun& r, int index) {
+    bh_hess* H = r.H; bh_proj* P = r.P; CgWorkspace& c = r.c; hipStream_t s = r.s;
+    const int mA = (int)P->mA;
+    const int64_t n = H->n;
+    ProjArgs pa = proj_args(P, c.d_state, true, true);
+    BH_TRY(cauchy_factor_solve(r, pa, index));
+    // a = G D g: one G v launch over the masked g (G rebuilt first when it is stale).  B = G D A' (n x mA): the GEMM of the
+    // row-space form over the n rows of G.  Pass 0, and again every kCauchyGramEqRefresh-th pass from the device-side mask,
+    // which by then holds the variable fixed by the decision in between: the row kernel behind a formation applies no update.
+    const bool form_ab = (index % kCauchyGramEqRefresh) == 0;
+    if (form_ab) {
+        hipLaunchKernelGGL(proj_mask_kernel, dim3(cauchy_mask_grid(n)), dim3(256), 0, s, r.a.g, H->vpad, (const int*)P->fixrank, (int)n,
+                           (const CgState*)c.d_state);
+        BH_TRY(launch_hmul(H, H->vpad, H->geq, c.d_state, -1));
+        hipLaunchKernelGGL(image_b_mfma_kernel, dim3((unsigned)((n + 127) / 128)), dim3(256), 0, s, (const double*)H->G, H->ld, n,
+                           (const double*)P->Ad, P->ldA, mA, (const int*)P->fixrank, H->geq + H->ld, H->ld, (const CgState*)c.d_state);
+        BH_HIP(hipGetLastError());
+    }
+    CauchyGramEqArgs ga{};
+    ga.st = c.d_state; ga.G = H->G; ga.ld = H->ld; ga.n = (int)n; ga.mA = mA; ga.a = H->geq; ga.B = H->geq + H->ld;
+    ga.A = P->Ad; ga.ldA = P->ldA; ga.tw = P->tw; ga.g = r.a.g; ga.Hd = c.Hp; ga.fresh = form_ab ? 1 : 0;
+    const int rblocks = (int)(H->ld / 16), dblocks = ((int)(n + 1) / 2 + 63) / 64;
+    hipLaunchKernelGGL(cauchy_gram_eq_kernel, dim3(rblocks + dblocks + mA), dim3(256), 0, s, ga, rblocks, dblocks, pa, (const double*)c.r,
+                       c.p, P->tpart);
+    hipLaunchKernelGGL(cauchy_advance_kernel, dim3(1), dim3(CA_T), 0, s, r.a);
+    BH_HIP(hipGetLastError());
+    return BH_OK;
+}
+
+static int32_t cauchy_launch_pass(CauchyRun& r, int index) {
+    switch (r.plan.form) {
+        case CAUCHY_ROWSPACE_BOX: return r.plan.fused ? cauchy_pass_rowspace_fused(r, index) : cauchy_pass_rowspace_box(r, index);
+        case CAUCHY_ROWSPACE_EQ: return cauchy_pass_rowspace_eq(r, index);
+        case CAUCHY_GRAM_EQ: return cauchy_pass_gram_eq(r, index);
+        default: return cauchy_pass_sweep(r, index);               // (CAUCHY_GRAM has no passes: one launch, see cauchy_impl)
+    }
+}
+
+// Counters of the handle and the record bh_cauchy_info reads, from the plan and the final progress word.
+static void cauchy_account(CauchyRun& r, const MirrorWord& mw, uint64_t launches_in) {
+    bh_hess* H = r.H; bh_proj* P = r.P;
+    const CauchyPlan& p = r.plan;
+    if (p.form == CAUCHY_SWEEP) H->stats.n_hmul += mw.n_hmul;  // (image-space search: passes, not sweeps over J)
+    // from G with equalities: the G v launches that ran — pass 0 and every kCauchyGramEqRefresh-th pass (those enqueued behind the end are gated off)
+    if (p.form == CAUCHY_GRAM_EQ) H->stats.n_hmul += 1 + std::max(mw.n_hmul - 1, 0) / kCauchyGramEqRefresh;
+    // option cauchy_image_refresh: the sweeps over J of the re-formations that ran — pass indices R, 2R, ... below the number of passes
+    // (those enqueued behind the end are gated off)
+    if (p.refresh > 0) H->stats.n_jv += (int64_t)r.reform_sweeps * (std::max(mw.n_hmul - 1, 0) / p.refresh);
+    P->last_cauchy_passes = mw.n_hmul;
+    P->last_cauchy_form = (int)p.form;
+    P->last_cauchy_launches = (int)(g_kernel_launches - launches_in);
+}
+
 // cauchy_step(x, g, H, chol_aat, lincons, delta) — src/basic_tralcnlss.jl:574-639, device-resident: initial
 // active_bounds! (poly:203-215), projection of -g, then per breakpoint one H*d, one projection and — instead of the
 // reference's O(p^3) host refactorisation (add_active! -> cholesky_aug_aat) — a rank-one downdate of A_free A_free' and an
 // mA x mA Cholesky on the device.  On return lincons' active set is the one the reference would hold (fix_chunks_out).
+// Which form runs: cauchy_make_plan (the rule: bh_cauchy_plan.h); its passes: cauchy_launch_pass.
 static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double* g, const double* xlow, const double* xupp, double delta,
                            double* s_out, uint64_t* fix_chunks_out, int32_t* n_breakpoints, int32_t* n_hmul_out, bool dev) {
     BH_REQUIRE_INIT();
@@ -3180,7 +3506,8 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     // (the Cauchy kernels read x, g and the bounds element by element: a device caller's vectors are used where they lie)
     if (!dev) BH_TRY(stage_vecs(c.x, {x, xlow, xupp, g}, n, c.n_pad));            // c.x, c.xlow, c.xupp, c.g are consecutive
 
-    CauchyArgs a{};
+    CauchyRun run{H, P, c, s};
+    CauchyArgs& a = run.a;
     a.st = c.d_state;
     a.x = dev ? x : c.x; a.g = dev ? g : c.g; a.xlow = dev ? xlow : c.xlow; a.xupp = dev ? xupp : c.xupp;
     a.negg = c.r; a.d = c.p; a.Hd = c.Hp; a.s = c.w; a.dl = c.wl; a.du = c.wu;
@@ -3191,250 +3518,18 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     if (c.tag == 0) c.tag = 1;
     a.mirror = c.d_mirror; a.tag = c.tag;
 
-    // Box constraints, one rank: the image-space search (bh_cauchy.hip.h) — t_d = J~ d once by the J v kernel, then per breakpoint
-    // a rank-one update of t_d, t_s over the rows (one column of J) + the single-workgroup advance kernel; no sweep over J.
-    // (several ranks: every rank keeps t_d, t_s for ITS rows; the two sums are all-reduced before the replicated advance kernel)
-    // With linear equalities the form costs 1 + mA J v sweeps up front: always used up to cauchy_image_max_ma rows; up to 64 rows when
-    // the previous search on this handle took more than 4 (1 + mA) passes (consecutive searches of a solve behave alike).
-    // Gram-form handle, box constraints, one rank, option "cauchy_gram": init -> G d -> cauchy_gram_kernel, the whole search in one
-    // launch (bh_cauchygram.hip.h).  Any other case takes the path it takes without the option.
-    const bool gram_search = g_ctx.opt_cauchy_gram != 0 && H->form == BH_HESS_GRAM && mA == 0 && !comm_active();
-    // Gram-form handle, 1 <= mA <= 64, one rank, option "cauchy_gram_eq": the linear-equality form in the column space of G
-    // (bh_cauchygrameq.hip.h) — a = G D g, B = G D A' from one G v launch and one GEMM over n rows, re-formed every
-    // kCauchyGramEqRefresh-th pass; per pass [factor + solves: y] -> [Hd = -a - B y | d = P(-g) | t_fresh] -> [decision from Hd].
-    const bool gram_eq = g_ctx.opt_cauchy_gram_eq != 0 && H->form == BH_HESS_GRAM && mA >= 1 && mA <= 64 && !comm_active() && P->ldA == H->ld;
-    const bool image = !gram_search && !gram_eq && g_ctx.opt_cauchy_image != 0 &&
-                       (mA == 0 || mA <= g_ctx.opt_cauchy_image_max_ma || (mA <= 64 && P->last_cauchy_passes > 4 * (1 + mA)));
-    const bool image_gen = image && mA > 0;
-    // ... and there ONE kernel per breakpoint: the decision of pass k-1 in the prologue of the row kernel of pass k (cauchy_fused_kernel)
-    const bool fused = image && !image_gen && !comm_active() && g_ctx.opt_cauchy_fused != 0;
-    // Option cauchy_image_refresh = R >= 1 (one rank): at every pass index that is a positive multiple of R the images are formed again
-    // from J and the device-side state, behind the `done` gate; the other passes are unchanged.  Several ranks: ignored.
-    //   one kernel per breakpoint: launch k -> [cauchy_fused_kernel, decide_only: decision k-1] [cauchy_reform_kernel: t_d, t_s, sums];
-    //                              a J wider than the register-resident kernels hold (n > 16384) keeps its carried images
-    //   two-kernel box form:       [J v of d] [J v of s_c] before cauchy_image_kernel(fresh = 1)
-    //   with equalities:           [mask g, J v: a] [B: the GEMM or mA masked sweeps] [J v of s_c] before the row kernel (fresh = 1)
-    const int refresh = (image && !comm_active() && !(fused && multi_panel(H))) ? (int)std::min<int64_t>(g_ctx.opt_cauchy_image_refresh, 0xfffff) : 0;
-    auto reforms_at = [&](int index) { return refresh > 0 && index > 0 && (index % refresh) == 0; };
-    int reform_sweeps = 0;                                            // sweeps over J of one re-formation, for stats.n_jv
-    const int64_t img_rows = H->d + H->q_eff;
-    const int reform_cfg = pick_config(std::min<int>(H->nchunks, (int)kMaxChunks));
-    const int reform_grid = std::min(kCauchyFusedGrid, grid_for(reform_cfg, img_rows));
-    const int img_grid = (int)std::max<int64_t>(1, std::min<int64_t>(fused ? kCauchyFusedGrid : kCauchyImgGrid, (img_rows + 255) / 256));
-    // (fewer, fatter workgroups measured slower: docs/design_history_r3.md)
-    const int fused_grid = (int)std::max<int64_t>(1, std::min<int64_t>(kCauchyFusedGrid, (img_rows + CA_T - 1) / CA_T));
-    // with equalities a workgroup takes tiles of 64 rows; the partial sums still have to fit the [2][kCauchyImgGrid] slot
-    const int gen_grid = (int)std::max<int64_t>(1, std::min<int64_t>(kCauchyImgGrid, (img_rows + 63) / 64));
-    const bool gen_tiled = mA > 16;                                   // (few equalities: one row per thread, see bh_cauchy.hip.h)
-    const int part_G = (image_gen && gen_tiled) ? gen_grid : img_grid;   // how many partial sums a row kernel leaves
-    const int64_t img_cap = (std::max<int64_t>(H->d + H->q, 1) + 1) / 2 * 2;              // rows, rounded up to even (16-byte aligned tails)
-    double* img_scal = nullptr;
-    if (image) {
-        BH_TRY(hess_ready(H));
-        if (!H->timg) BH_TRY(dev_alloc(&H->timg, 2 * img_cap + 2 * kCauchyImgGrid + 16));
-        img_scal = H->timg + 2 * img_cap + 2 * kCauchyImgGrid;
-        a.img_part = comm_active() ? img_scal : H->timg + 2 * img_cap;
-        a.img_G = comm_active() ? 1 : part_G;
-        if (image_gen && H->timg_gen_doubles < (int64_t)(1 + mA) * img_cap) {
-            dev_free(H->timg_gen);
-            H->timg_gen = nullptr; H->timg_gen_doubles = 0;
-            BH_TRY(dev_alloc(&H->timg_gen, (int64_t)(1 + mA) * img_cap));
-            H->timg_gen_doubles = (int64_t)(1 + mA) * img_cap;
-        }
-    }
-
-    if (gram_eq && H->geq_doubles < (int64_t)(1 + mA) * H->ld) {
-        if (H->geq) BH_HIP(hipStreamSynchronize(s));              // (launches of an earlier search may still be queued)
-        dev_free(H->geq);
-        H->geq = nullptr; H->geq_doubles = 0;
-        BH_TRY(dev_alloc(&H->geq, (int64_t)(1 + mA) * H->ld));
-        H->geq_doubles = (int64_t)(1 + mA) * H->ld;
-    }
-
-    CauchyPass* pp = nullptr;
-    double* part_pp[2] = {nullptr, nullptr};
-    double* sbuf[2] = {c.w, c.Hp};                                     // s_c ping-pong of the fused form (H*d is never formed there)
-    if (fused) {
-        pp = reinterpret_cast<CauchyPass*>(img_scal + 8);             // 2 x 32 bytes in the 16-double tail of timg
-        part_pp[0] = H->timg + 2 * img_cap; part_pp[1] = part_pp[0] + 2 * kCauchyFusedGrid;
-        a.fixpass = reinterpret_cast<int*>(c.v); a.pp0 = pp;
-    }
+    run.plan = cauchy_make_plan(H, P);
+    const CauchyPlan& plan = run.plan;
+    run.img_rows = H->d + H->q_eff;
+    run.img_cap = (std::max<int64_t>(H->d + H->q, 1) + 1) / 2 * 2;
+    BH_TRY(cauchy_ensure_buffers(run));
     P->active_set = false;             // device mask is authoritative until adopt_mask below
     hipLaunchKernelGGL(cauchy_init_kernel, dim3(1), dim3(CG_T), 0, s, a);
     if (mA > 0) BH_TRY(launch_reduced_factor(P, true, nullptr));
-    const int max_pass = (int)(n + 1);
+    const int max_pass = plan.max_pass;
     int launched = 0;
-    auto launch_pass = [&](int index) -> int32_t {
-        if (fused && index > 0) {
-            CauchyFusedArgs fa{};
-            fa.pp = pp; fa.k = index; fa.g = a.g; fa.dl = a.dl; fa.du = a.du; fa.sbuf[0] = sbuf[0]; fa.sbuf[1] = sbuf[1];
-            fa.fixpass = a.fixpass; fa.fixrank = P->fixrank; fa.n = (int)n; fa.nmm = a.nmm;
-            fa.J = H->Jd; fa.ld = H->ld; fa.nrows = img_rows; fa.d_rows = H->d; fa.mu = H->mu;
-            fa.td = H->timg; fa.ts = H->timg + img_cap;
-            fa.part_in = part_pp[(index - 1) & 1]; fa.Gin = index == 1 ? img_grid : reforms_at(index - 1) ? reform_grid : fused_grid;
-            fa.part_out = part_pp[index & 1];
-            fa.mirror = a.mirror; fa.tag = a.tag;
-            if (reforms_at(index)) {
-                // decision index-1 alone (every group of 64 elements of s_c has its owner at any grid), then both images from J
-                fa.decide_only = 1;
-                const int dec_grid = (int)std::max<int64_t>(1, std::min<int64_t>(fused_grid, (n + 63) / 64));
-                hipLaunchKernelGGL(cauchy_fused_kernel, dim3(dec_grid), dim3(CA_T), 0, s, fa);
-                CauchyReformArgs ra{};
-                ra.gate = pp + (index & 1); ra.k = index; ra.g = a.g; ra.fixpass = a.fixpass; ra.n = (int)n; ra.s = sbuf[index & 1];
-                ra.J = H->Jd; ra.ld = H->ld; ra.nrows = img_rows; ra.d_rows = H->d; ra.mu = H->mu; ra.nchunks = H->nchunks;
-                ra.td = fa.td; ra.ts = fa.ts; ra.part = part_pp[index & 1];
-                launch_cauchy_reform(reform_cfg, ra, reform_grid, s);
-                reform_sweeps = 1;
-                BH_HIP(hipGetLastError());
-                return BH_OK;
-            }
-            hipLaunchKernelGGL(cauchy_fused_kernel, dim3(fused_grid), dim3(CA_T), 0, s, fa);
-            BH_HIP(hipGetLastError());
-            return BH_OK;
-        }
-        if (fused) {                                                   // launch 0: t_d = J~ d_0 (:609 in the row space), t_s = 0, their sums
-            CauchyImgArgs ia{};
-            ia.st = c.d_state; ia.J = H->Jd; ia.ld = H->ld; ia.nrows = img_rows; ia.d_rows = H->d; ia.mu = H->mu;
-            ia.td = H->timg; ia.ts = H->timg + img_cap; ia.part = part_pp[0]; ia.first = 1;
-            BH_TRY(launch_jv(H, c.p, H->timg, true, nullptr));
-            H->stats.n_jv += 1;
-            hipLaunchKernelGGL(cauchy_image_kernel, dim3(img_grid), dim3(256), 0, s, ia);
-            BH_HIP(hipGetLastError());
-            return BH_OK;
-        }
-        if (image) {
-            const int64_t rows_cap = img_cap;
-            CauchyImgArgs ia{};
-            ia.st = c.d_state; ia.J = H->Jd; ia.ld = H->ld; ia.nrows = img_rows; ia.d_rows = H->d; ia.mu = H->mu;
-            ia.td = H->timg; ia.ts = H->timg + rows_cap; ia.part = H->timg + 2 * rows_cap; ia.first = index == 0 ? 1 : 0;
-            ia.fresh = reforms_at(index) ? 1 : 0;
-            if (image_gen) {
-                // factor of the current active set and y = (A_free A_free')^{-1} A_free(-g) (left in P->tw), as in the sweeping form
-                // Three launches per pass (image_gen implies mA <= 64): [downdate + refactorisation + right-hand side + the two solves: y]
-                // -> [rows | d = P(-g) | t_fresh = A_free(-g) for the next pass] -> [decision]
-                ProjArgs pa = proj_args(P, c.d_state, true, true);
-                if (index > 0) {
-                    P->linv_valid = false;
-                    hipLaunchKernelGGL(cauchy_factor_solve_kernel, dim3(1), dim3(256), 0, s, P->M, P->Lr, mA, P->info, pa, (const double*)c.r,
-                                       (const double*)P->tpart, (const CgState*)c.d_state);
-                } else {
-                    hipLaunchKernelGGL(proj_left_mul_kernel, dim3(mA), dim3(256), 0, s, pa, (const double*)c.r);     // t (:86-98), then y
-                    hipLaunchKernelGGL(trsv_small_kernel, dim3(1), dim3(256), 0, s, pa);
-                }
-                BH_HIP(hipGetLastError());
-                if (index == 0 || ia.fresh) {
-                    // (index > 0: the re-formation of option cauchy_image_refresh, from the device-side mask — which holds the variable
-                    // the decision of pass index-1 fixed — and gated by `done`; t_s = J~ s_c from the s_c that decision left)
-                    const CgState* gate = index == 0 ? nullptr : (const CgState*)c.d_state;
-                    // a = J~ D g: one J v sweep over the masked g.  B = J~ D A' (rows x mA): ONE sweep on the matrix cores
-                    // (image_b_mfma_kernel) when the images share their leading dimension, else mA J v sweeps over masked rows of A
-                    const int mgrid = std::max(1, std::min((int)((n + 255) / 256), 1024));
-                    const bool gemm = g_ctx.opt_cauchy_gemm != 0 && P->ldA == H->ld;
-                    for (int j = -1; j < (gemm ? 0 : mA); ++j) {
-                        const double* src = (j < 0) ? a.g : (const double*)(P->Ad + (int64_t)j * P->ldA);
-                        hipLaunchKernelGGL(proj_mask_kernel, dim3(mgrid), dim3(256), 0, s, src, H->vpad, (const int*)P->fixrank, (int)n, gate);
-                        BH_TRY(launch_jv(H, H->vpad, H->timg_gen + (int64_t)(j + 1) * rows_cap, true, nullptr, gate));
-                        if (index == 0) H->stats.n_jv += 1;
-                    }
-                    if (gemm && img_rows > 0) {                 // (a rank without rows has no rows of B)
-                        hipLaunchKernelGGL(image_b_mfma_kernel, dim3((unsigned)((img_rows + 127) / 128)), dim3(256), 0, s, (const double*)H->Jd, H->ld,
-                                           img_rows, (const double*)P->Ad, P->ldA, mA, (const int*)P->fixrank, H->timg_gen + rows_cap, rows_cap, gate);
-                        BH_HIP(hipGetLastError());
-                    }
-                    if (index > 0) {
-                        BH_TRY(launch_jv(H, c.w, H->timg + rows_cap, true, nullptr, gate));
-                        reform_sweeps = (gemm ? 1 : 1 + mA) + 1;
-                    }
-                }
-                CauchyImgGenArgs ga{};
-                ga.b = ia; ga.a = H->timg_gen; ga.B = H->timg_gen + rows_cap; ga.rows_cap = rows_cap; ga.mA = mA;
-                ga.A = P->Ad; ga.ldA = P->ldA; ga.tw = P->tw; ga.g = a.g;
-                const int dblocks = ((int)(n + 1) / 2 + 63) / 64;
-                hipLaunchKernelGGL(cauchy_gen_rows_and_d_kernel, dim3(part_G + dblocks + mA), dim3(256), 0, s, ga, gen_tiled ? 1 : 0, part_G, dblocks, pa,
-                                   (const double*)c.r, c.p, P->tpart);
-            } else {
-                if (index == 0) {
-                    BH_TRY(launch_jv(H, c.p, H->timg, true, nullptr));              // t_d = J~ d_0 (:609 in the row space)
-                    H->stats.n_jv += 1;
-                }
-                if (ia.fresh) {
-                    // t_d = J~ d from the d the advance kernel keeps (d[ind] is zero already), t_s = J~ s_c: gated by `done`
-                    BH_TRY(launch_jv(H, c.p, H->timg, true, nullptr, (const CgState*)c.d_state));
-                    BH_TRY(launch_jv(H, c.w, H->timg + rows_cap, true, nullptr, (const CgState*)c.d_state));
-                    reform_sweeps = 2;
-                }
-                hipLaunchKernelGGL(cauchy_image_kernel, dim3(img_grid), dim3(256), 0, s, ia);
-            }
-            if (comm_active()) {
-                hipLaunchKernelGGL(cauchy_image_sum_kernel, dim3(1), dim3(64), 0, s, (const double*)ia.part, part_G, img_scal, (const CgState*)c.d_state);
-                BH_TRY(allreduce_inplace(img_scal, 2, H, c.d_state));
-            }
-            hipLaunchKernelGGL(cauchy_advance_kernel, dim3(1), dim3(CA_T), 0, s, a);
-            BH_HIP(hipGetLastError());
-            return BH_OK;
-        }
-        if (gram_eq) {
-            ProjArgs pa = proj_args(P, c.d_state, true, true);
-            if (index > 0) {
-                P->linv_valid = false;
-                hipLaunchKernelGGL(cauchy_factor_solve_kernel, dim3(1), dim3(256), 0, s, P->M, P->Lr, mA, P->info, pa, (const double*)c.r,
-                                   (const double*)P->tpart, (const CgState*)c.d_state);
-            } else {
-                hipLaunchKernelGGL(proj_left_mul_kernel, dim3(mA), dim3(256), 0, s, pa, (const double*)c.r);     // t (:86-98), then y
-                hipLaunchKernelGGL(trsv_small_kernel, dim3(1), dim3(256), 0, s, pa);
-            }
-            BH_HIP(hipGetLastError());
-            // a = G D g: one G v launch over the masked g (G rebuilt first when it is stale).  B = G D A' (n x mA): the GEMM of the
-            // row-space form over the n rows of G.  Pass 0, and again every kCauchyGramEqRefresh-th pass from the device-side mask,
-            // which by then holds the variable fixed by the decision in between: the row kernel behind a formation applies no update.
-            const bool form_ab = (index % kCauchyGramEqRefresh) == 0;
-            if (form_ab) {
-                const int mgrid = std::max(1, std::min((int)((n + 255) / 256), 1024));
-                hipLaunchKernelGGL(proj_mask_kernel, dim3(mgrid), dim3(256), 0, s, a.g, H->vpad, (const int*)P->fixrank, (int)n, (const CgState*)c.d_state);
-                BH_TRY(launch_hmul(H, H->vpad, H->geq, c.d_state, -1));
-                hipLaunchKernelGGL(image_b_mfma_kernel, dim3((unsigned)((n + 127) / 128)), dim3(256), 0, s, (const double*)H->G, H->ld, n,
-                                   (const double*)P->Ad, P->ldA, mA, (const int*)P->fixrank, H->geq + H->ld, H->ld, (const CgState*)c.d_state);
-                BH_HIP(hipGetLastError());
-            }
-            CauchyGramEqArgs ga{};
-            ga.st = c.d_state; ga.G = H->G; ga.ld = H->ld; ga.n = (int)n; ga.mA = mA; ga.a = H->geq; ga.B = H->geq + H->ld;
-            ga.A = P->Ad; ga.ldA = P->ldA; ga.tw = P->tw; ga.g = a.g; ga.Hd = c.Hp; ga.fresh = form_ab ? 1 : 0;
-            const int rblocks = (int)(H->ld / 16), dblocks = ((int)(n + 1) / 2 + 63) / 64;
-            hipLaunchKernelGGL(cauchy_gram_eq_kernel, dim3(rblocks + dblocks + mA), dim3(256), 0, s, ga, rblocks, dblocks, pa, (const double*)c.r,
-                               c.p, P->tpart);
-            hipLaunchKernelGGL(cauchy_advance_kernel, dim3(1), dim3(CA_T), 0, s, a);
-            BH_HIP(hipGetLastError());
-            return BH_OK;
-        }
-        if (index > 0 && mA > 0) {
-            // chol_downdate = 1 only has a case where refactoring is expensive (mA > 64: blocked factorisation, 0.21 ms at mA = 256);
-            // up to 64 rows the register-panel Cholesky (18.5 us) costs what the rank-one downdate costs (20 us), so the factor is
-            // always rebuilt from the downdated Gram matrix there — as accurate as the reference's from-scratch rebuild.
-            const bool factor_downdate = g_ctx.opt_chol_downdate && mA > 64;
-            if (factor_downdate && (index % kDowndateRefresh) == 0) {
-                // every kDowndateRefresh-th breakpoint the factor is rebuilt from the device-side mask: hyperbolic downdates lose
-                // accuracy cumulatively, and without bound once A_free A_free' approaches singularity (c = sqrt(1 - s^2) -> 0)
-                BH_TRY(launch_reduced_factor(P, true, (const CgState*)c.d_state));
-            } else if (factor_downdate) {
-                P->M_valid = false;     // only the factor follows the active set on this path
-                // add_active!: one more fixed variable = rank-one downdate of chol(A_free A_free'), O(mA^2)
-                P->linv_valid = false;
-                hipLaunchKernelGGL(chol_downdate_kernel, dim3(1), dim3(CG_T), (size_t)mA * sizeof(double), s, P->Lr, (const double*)P->Ad,
-                                   P->ldA, mA, P->info, (const CgState*)c.d_state);
-            } else {
-                // refactor from the downdated Gram matrix, O(mA^3)
-                hipLaunchKernelGGL(gram_downdate_kernel, dim3(std::max(1, (mA * mA + 255) / 256)), dim3(256), 0, s, P->M, P->Ad, P->ldA, mA,
-                                   (const CgState*)c.d_state);
-                BH_TRY(launch_chol(P, (const CgState*)c.d_state));
-            }
-        }
-        if (mA > 0) BH_TRY(launch_project(P, c.r, c.p, c.d_state, true));       // d = P(-g)   :592 / :632  (box: kept in place)
-        BH_TRY(launch_hmul(H, c.p, c.Hp, c.d_state, -1));           // Hd = H*d    :609 / :633
-        hipLaunchKernelGGL(cauchy_advance_kernel, dim3(1), dim3(CA_T), 0, s, a);
-        BH_HIP(hipGetLastError());
-        return BH_OK;
-    };
     MirrorWord mw{};
+    const bool gram_search = plan.form == CAUCHY_GRAM;
     if (gram_search) {
         BH_TRY(launch_hmul(H, c.p, c.Hp, c.d_state, -1));           // Hd = H*d    :609  (rebuilds G first when it is stale)
         H->stats.n_hmul += 1;
@@ -3445,14 +3540,13 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
         BH_HIP(hipGetLastError());
         launched = max_pass;                                        // the kernel publishes once, when its loop has ended
     }
-    // image-space passes take ~17 us: keep a deeper queue ahead of the GPU (over RCCL every over-launched pass costs a collective)
-    const int batch = (!image && !gram_eq) ? launch_batch_size(H) : (comm_active() && !use_peer_path()) ? 4 : 8;
+    const int batch = plan.batch;
     // (fused form: launch k carries decision k-1, so `launched` launches stand for launched - 1 passes)
-    const int off = fused ? 1 : 0;
+    const int off = plan.off;
     const int max_launch = max_pass + off;
     auto launch_batch = [&](int nb) -> int32_t {
         nb = std::min(nb, max_launch - launched);
-        for (int i = 0; i < nb; ++i) BH_TRY(launch_pass(launched + i));
+        for (int i = 0; i < nb; ++i) BH_TRY(cauchy_launch_pass(run, launched + i));
         launched += nb;
         return BH_OK;
     };
@@ -3469,18 +3563,10 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     }
     BH_TRY(wait_mirror(c, a.tag, launched - off, &mw));
     // (fused form: decision j is taken by launch j+1, which writes s_c into buffer (j+1) & 1)
-    BH_TRY(fetch_vec(s_out, fused ? sbuf[mw.n_hmul & 1] : c.w, n, dev));
+    BH_TRY(fetch_vec(s_out, plan.fused ? run.sbuf[mw.n_hmul & 1] : c.w, n, dev));
     int info_host = 0;
     BH_TRY(adopt_device_mask(P, fix_chunks_out, &info_host));     // drains the stream; canonical fixrank / fixidx, P->nfix
-    if (!image && !gram_search && !gram_eq) H->stats.n_hmul += mw.n_hmul;  // (image-space search: passes, not sweeps over J)
-    // from G with equalities: the G v launches that ran — pass 0 and every kCauchyGramEqRefresh-th pass (those enqueued behind the end are gated off)
-    if (gram_eq) H->stats.n_hmul += 1 + std::max(mw.n_hmul - 1, 0) / kCauchyGramEqRefresh;
-    // option cauchy_image_refresh: the sweeps over J of the re-formations that ran — pass indices R, 2R, ... below the number of passes
-    // (those enqueued behind the end are gated off)
-    if (refresh > 0) H->stats.n_jv += (int64_t)reform_sweeps * (std::max(mw.n_hmul - 1, 0) / refresh);
-    P->last_cauchy_passes = mw.n_hmul;
-    P->last_cauchy_form = gram_search ? 3 : gram_eq ? 4 : !image ? 0 : image_gen ? 2 : 1;
-    P->last_cauchy_launches = (int)(g_kernel_launches - launches_in);
+    cauchy_account(run, mw, launches_in);
     if (!mw.done) return fail(BH_ERR_HIP, "internal: Cauchy loop did not terminate");
     if (n_breakpoints) *n_breakpoints = mw.iter;
     if (n_hmul_out) *n_hmul_out = mw.n_hmul;

@@ -127,14 +127,19 @@ def test_host_counts_only_the_reformations_that_ran():
     behind the end are gated; the kernel gates before its first load; the gated sweeps carry the loop state."""
     csrc = os.path.join(ROOT, "benlsip.jl_amd", "csrc")
     src = open(os.path.join(csrc, "bh_api.hip")).read()
-    impl = src[src.index("static int32_t cauchy_impl("):src.index("int32_t bh_cauchy_step(")]
-    assert re.search(r"if \(refresh > 0\) H->stats\.n_jv \+= \(int64_t\)reform_sweeps \* \(std::max\(mw\.n_hmul - 1, 0\) / refresh\);", impl)
-    loop = impl[:impl.index("MirrorWord mw{}")]
-    # inside launch_pass the counter moves for pass 0 only
-    for m in re.finditer(r"H->stats\.n_jv \+= 1;", loop):
-        before = loop[max(0, m.start() - 400):m.start()]
+    impl = src[src.index("struct CauchyPlan {"):src.index("int32_t bh_cauchy_step(")]           # plan, launchers, accounting, cauchy_impl
+    account = impl[impl.index("static void cauchy_account("):impl.index("static int32_t cauchy_impl(")]
+    assert re.search(r"if \(p\.refresh > 0\) H->stats\.n_jv \+= \(int64_t\)r\.reform_sweeps \* \(std::max\(mw\.n_hmul - 1, 0\) / p\.refresh\);", account)
+    assert impl.index("cauchy_account(run, mw, launches_in);") > impl.index("BH_TRY(wait_mirror(c, a.tag, launched - off, &mw));")
+    passes = impl[impl.index("static int32_t cauchy_pass_sweep("):impl.index("static int32_t cauchy_launch_pass(")]
+    # inside the launchers of a pass the counter moves for pass 0 only
+    assert len(re.findall(r"H->stats\.n_jv \+= 1;", passes)) == 3 and "stats.n_jv" not in account.replace("if (p.refresh > 0) H->stats.n_jv", "")
+    for m in re.finditer(r"H->stats\.n_jv \+= 1;", passes):
+        before = passes[max(0, m.start() - 400):m.start()]
         assert "index == 0" in before or "launch 0" in before, before[-200:]
-    assert "!comm_active()" in impl[impl.index("const int refresh ="):impl.index("auto reforms_at")]
+    rule = open(os.path.join(csrc, "bh_cauchy_plan.h")).read()
+    assert re.search(r"if \(image && !in\.comm && [^\n]*\) o\.refresh = ", rule)
+    assert "p.refresh = sel.refresh;" in impl
     assert len(re.findall(r"launch_jv\(H, c\.[pw], [^;]*\(const CgState\*\)c\.d_state\)\);", impl)) == 2           # two-kernel box form
     assert re.search(r"launch_jv\(H, c\.w, H->timg \+ rows_cap, true, nullptr, gate\)", impl)                       # equalities: t_s
     ker = open(os.path.join(csrc, "bh_cauchy.hip.h")).read()

@@ -41,7 +41,16 @@ def test_gram_cg_fused_needs_an_initialised_device():
 def test_gram_cg_kernel_is_dispatched_for_every_geometry_from_a_function_of_its_own():
     api = open(os.path.join(ROOT, "benlsip.jl_amd", "csrc", "bh_api.hip")).read()
     assert '#include "bh_gramcg.hip.h"' in open(os.path.join(ROOT, "benlsip.jl_amd", "csrc", "bh_kernels.hip.h")).read()
-    m = re.search(r"const\s+RsConfig\s+kRsConfigs\[\]\s*=\s*\{(.*?)\n\};", api, flags=re.S)
-    table = [tuple(int(x) for x in r) for r in re.findall(r"\{\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*,\s*\d+\s*\}", m.group(1))]
-    inst = [tuple(int(x) for x in r) for r in re.findall(r"(?:case \d+|default): launch_gram_cg_geom<(\d+), (\d+), (\d+)>", api)]
-    assert inst == table
+    # launch_gram_cg goes through the one geometry dispatcher and launches both prologue variants in the geometry it is handed;
+    # gram_cg_kernel is launched nowhere else
+    m = re.search(r"void\s+launch_gram_cg\s*\(\s*int\s+cfg\s*,[^{]*\{(.*?)\n\}", api, flags=re.S)
+    assert m, "launch_gram_cg not found"
+    body = m.group(1)
+    assert "with_rs_geom(cfg," in body and "using G = decltype(geom);" in body
+    inst = re.findall(r"gram_cg_kernel<G::T, G::CPT, G::R, (\d)>\), dim3\(grid\), dim3\(G::T\), 0, s, a\)", body)
+    assert inst == ["1", "0"]
+    assert api.count("gram_cg_kernel<") == 2
+    # with_rs_geom hands out every entry of the geometry list
+    geoms = re.search(r"using\s+RsGeoms\s*=\s*std::tuple<(.*?)\n\s*>;", api, flags=re.S).group(1)
+    n = len(re.findall(r"RsGeom<\s*\d+\s*,\s*\d+\s*,\s*\d+\s*,\s*\d+\s*>", geoms))
+    assert n == 7 and len(re.findall(r"f\(std::tuple_element_t<\d+, RsGeoms>\{\}\)", api)) == n

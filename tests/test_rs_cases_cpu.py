@@ -1,7 +1,7 @@
 """tests/rs_cases.py against the source it mirrors, and against the coverage it promises.
 
-1. kRsConfigs, pick_config, kMaxChunks, kMaxBlocksPerCu, kPanelChunks, kPanelCfg, the template arguments of launch_row_stream,
-   grid_for and gram_geometry are parsed out of csrc/bh_api.hip, GNG_BS out of csrc/bh_gngram.hip.h: a retuned geometry
+1. The geometry list RsGeoms (kRsConfigs is built from it), pick_config, kMaxChunks, kMaxBlocksPerCu, kPanelChunks, kPanelCfg, the
+   switch of with_rs_geom, grid_for and gram_geometry are parsed out of csrc/bh_api.hip, GNG_BS out of csrc/bh_gngram.hip.h: a retuned geometry
    must be carried over to the mirror, or tests/test_row_stream_exact_gpu.py would silently fall back to single-pass shapes.
 2. For 256 compute units (MI355X) and two other counts the conditions of the coverage table in rs_cases.py are evaluated from
    the mirror: per path both n, passes ending on either register buffer, the grid-sized and grid + 1 row-group counts, full and
@@ -44,10 +44,13 @@ def _body(text, signature_regex):
 
 def test_mirror_matches_the_launch_geometry_in_the_source():
     api = _src("bh_api.hip")
-    m = re.search(r"const\s+RsConfig\s+kRsConfigs\[\]\s*=\s*\{(.*?)\n\};", api, flags=re.S)
-    assert m, "kRsConfigs not found"
-    rows = [tuple(int(x) for x in r) for r in re.findall(r"\{\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*\}", m.group(1))]
+    # the one list of geometries: kRsConfigs is built from it, every launcher reaches it through with_rs_geom
+    m = re.search(r"using\s+RsGeoms\s*=\s*std::tuple<(.*?)\n\s*>;", api, flags=re.S)
+    assert m, "RsGeoms not found"
+    rows = [tuple(int(x) for x in r) for r in re.findall(r"RsGeom<\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*>", m.group(1))]
     assert rows == rc.RS_CONFIGS
+    assert "constexpr auto kRsConfigs = rs_config_table(RsGeoms{});" in api
+    assert "RsConfig{G::T, G::CPT, G::R, G::blocks_per_cu}..." in api
     # pick_config: a chain of `if (nchunks <= t) return i;` and a final return
     body = _body(api, r"int\s+pick_config\s*\(\s*int\s+nchunks\s*\)\s*\{")
     chain = [(int(t), int(i)) for t, i in re.findall(r"if \(nchunks <= (\d+)\) return (\d+);", body)]
@@ -60,13 +63,18 @@ def test_mirror_matches_the_launch_geometry_in_the_source():
     assert _const(api, "kPanelChunks") == rc.K_PANEL_CHUNKS
     assert _const(api, "kPanelCfg") == rc.K_PANEL_CFG
     assert _const(_src("bh_gngram.hip.h"), "GNG_BS") == rc.GNG_BS
-    # the switch that turns an index into a template instantiation must agree with the table
-    body = _body(api, r"void\s+launch_row_stream\s*\(\s*int\s+cfg\s*,")
-    inst = re.findall(r"(case (\d+)|default): launch_rs_mode(?:_vlds)?<(\d+), (\d+), (\d+)>", body)
+    # the switch that turns an index into a geometry walks the list in order, the last entry as the default; no triple is
+    # written anywhere else (a second table could drift from the first)
+    body = _body(api, r"void\s+with_rs_geom\s*\(\s*int\s+cfg\s*,")
+    inst = re.findall(r"(case (\d+)|default): f\(std::tuple_element_t<(\d+), RsGeoms>\{\}\); break;", body)
     assert len(inst) == len(rc.RS_CONFIGS)
-    for k, (_, idx, T, CPT, R) in enumerate(inst):
-        assert (int(idx) if idx else len(inst) - 1) == k
-        assert (int(T), int(CPT), int(R)) == rc.RS_CONFIGS[k][:3]
+    for k, (_, idx, elem) in enumerate(inst):
+        assert (int(idx) if idx else len(inst) - 1) == k == int(elem)
+    assert len(re.findall(r"switch \(cfg\)", api)) == 1
+    for T, CPT, R, _ in rc.RS_CONFIGS:
+        assert len(re.findall(r"<\s*%d\s*,\s*%d\s*,\s*%d\s*[,>]" % (T, CPT, R), re.sub(r"//[^\n]*", "", api))) == 1, (T, CPT, R)
+    body = _body(api, r"void\s+launch_row_stream\s*\(\s*int\s+cfg\s*,")
+    assert "with_rs_geom(cfg," in body and "launch_rs_mode<G>(mode, a, grid, s);" in body
     # the wide image is swept in panels above kMaxChunks, every panel with kPanelCfg; the Gram form stops at the same n
     assert "return H->nchunks > kMaxChunks;" in _body(api, r"bool\s+multi_panel\s*\(")
     assert re.search(r"H->ld\s*=\s*round_up\(std::max<int64_t>\(H->n,\s*1\),\s*16\);\s*H->nchunks\s*=\s*\(int\)\(H->ld\s*/\s*2\);", api)
