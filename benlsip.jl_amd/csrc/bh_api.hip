@@ -3,6 +3,7 @@
 // exports return once the host has what it is owed (option final_sync).
 #include "../../include/benlsip_hip.h"
 #include "bh_cauchy_plan.h"
+#include "bh_gram_ingest_plan.h"
 #include "bh_kernels.hip.h"
 
 #include <dlfcn.h>
@@ -91,6 +92,13 @@ struct AsyncUpload {
     hipEvent_t copied[2] = {nullptr, nullptr}, freed[2] = {nullptr, nullptr};
     size_t staging_bytes = 0;        // capacity of each staging buffer
     int64_t chunk_cols = 0;
+    // option gram_ingest: G is built behind the transposes, on a stream of its own (bh_gram_ingest_plan.h)
+    bool gram = false;               // this upload builds G of its handle
+    double gram_mu = 0.0;            // ... with this mu (the handle's at creation)
+    GramIngestPlan gram_plan{};
+    hipStream_t s_gram = nullptr;
+    double* gram_part = nullptr;     // per-slab partial blocks of one step (kept with the other resources)
+    int64_t gram_part_doubles = 0;
     bool resources() const { return s_copy != nullptr; }
 };
 
@@ -140,6 +148,7 @@ struct Ctx {
     int64_t opt_cg_fused = 1;        // box CG: two kernels per iteration (H*p with the p-update folded in + reduce/update) instead of three
     int64_t opt_proj_form = 1;       // 1: reduced mA x mA form (fast), 0: the reference's augmented mpp x mpp form
     int64_t opt_upload_chunk_mb = 64; // bh_hess_create_async: MiB of J per pipelined column chunk
+    int64_t opt_gram_ingest = 0;     // bh_hess_create_async, one rank, n <= 16384: the handle is born in the Gram form, G built during the upload
     int64_t opt_ev_stride = 8;       // BH_FLAG_PROFILE: hipEvents around every opt_ev_stride-th H*p launch of a handle
     // RCCL
     void* rccl_lib = nullptr;
@@ -693,6 +702,7 @@ int32_t launch_gram_build(bh_hess* H) {
 }
 
 int32_t ensure_gram(bh_hess* H) {
+    if (H->up) BH_TRY(hess_ready(H));        // an upload that builds G itself (option gram_ingest) leaves it valid
     if (H->G_valid) return BH_OK;
     return launch_gram_build(H);
 }
@@ -836,8 +846,10 @@ static void async_upload_destroy(AsyncUpload* u) {
         if (u->freed[i]) (void)hipEventDestroy(u->freed[i]);
         dev_free(u->staging[i]);
     }
+    dev_free(u->gram_part);
     if (u->s_copy) (void)hipStreamDestroy(u->s_copy);
     if (u->s_xpose) (void)hipStreamDestroy(u->s_xpose);
+    if (u->s_gram) (void)hipStreamDestroy(u->s_gram);
     delete u;
 }
 // A finished upload hands its streams / events / staging buffers to the next one (creating them costs ~3 ms, hipFree of the
@@ -858,27 +870,49 @@ static void async_upload_worker(bh_hess* H, const double* J, int64_t d, int64_t 
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) { bad("hipSetDevice (upload thread)", e); return; }
     const int64_t cc = u.chunk_cols;
+    // option gram_ingest: behind the transpose of chunk k, the blocks of G whose columns are all in the image by then
+    // (gram_ingest_step), on s_gram — never on s_xpose, where a Gram kernel of several milliseconds ahead of a transpose would hold
+    // that transpose's staging slot and with it the copy.  No launch reads a column that has not landed: a recycled image may hold
+    // stale data there.
+    auto gram_step = [&](int k, hipEvent_t xposed) -> bool {
+        const GramIngestStep st = gram_ingest_step(u.gram_plan, k);
+        if (st.nblocks == 0) return true;
+        if ((e = hipStreamWaitEvent(u.s_gram, xposed, 0)) != hipSuccess) { bad("hipStreamWaitEvent (Gram step)", e); return false; }
+        double* part = st.nslabs > 1 ? u.gram_part : nullptr;
+        hipLaunchKernelGGL(gn_gram_panel_kernel, dim3((unsigned)st.nblocks, (unsigned)st.nslabs), dim3(GNG_T), 0, u.s_gram,
+                           (const double*)H->Jd, H->ld, H->d + H->q_eff, H->d, u.gram_mu, st.slab_rows, (int)st.block_lo, H->G, part);
+        if (part != nullptr) {
+            const int64_t blocks = std::min<int64_t>(st.nblocks * (GNG_BS * GNG_BS / 256), (int64_t)u.gram_plan.n_cu * 8);
+            hipLaunchKernelGGL(gn_gram_panel_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, u.s_gram, (const double*)part,
+                               (int)st.nslabs, (int)st.nblocks, (int)st.block_lo, H->ld, H->G);
+        }
+        if ((e = hipGetLastError()) != hipSuccess) { bad("Gram step launch", e); return false; }
+        return true;
+    };
     int k = 0;
     for (int64_t c0 = 0; c0 < n; c0 += cc, ++k) {
         const int slot = k & 1;
         const int64_t cols = std::min(cc, n - c0);
         const bool last = c0 + cols >= n;
         // the staging slot is free once the transpose that read it (two chunks ago) has finished
-        if (k >= 2 && (e = hipEventSynchronize(u.freed[slot])) != hipSuccess) { bad("hipEventSynchronize", e); return; }
+        if (k >= 2 && (e = hipEventSynchronize(u.freed[slot])) != hipSuccess) { bad("hipEventSynchronize", e); break; }
         if (ldJ == d) e = hipMemcpyAsync(u.staging[slot], J + c0 * ldJ, (size_t)d * cols * sizeof(double), hipMemcpyHostToDevice, u.s_copy);
         else e = hipMemcpy2DAsync(u.staging[slot], (size_t)d * sizeof(double), J + c0 * ldJ, (size_t)ldJ * sizeof(double),
                                   (size_t)d * sizeof(double), (size_t)cols, hipMemcpyHostToDevice, u.s_copy);
-        if (e != hipSuccess) { bad("hipMemcpyAsync (J chunk)", e); return; }
-        if ((e = hipEventRecord(u.copied[slot], u.s_copy)) != hipSuccess) { bad("hipEventRecord", e); return; }
-        if ((e = hipStreamWaitEvent(u.s_xpose, u.copied[slot], 0)) != hipSuccess) { bad("hipStreamWaitEvent", e); return; }
+        if (e != hipSuccess) { bad("hipMemcpyAsync (J chunk)", e); break; }
+        if ((e = hipEventRecord(u.copied[slot], u.s_copy)) != hipSuccess) { bad("hipEventRecord", e); break; }
+        if ((e = hipStreamWaitEvent(u.s_xpose, u.copied[slot], 0)) != hipSuccess) { bad("hipStreamWaitEvent", e); break; }
         const int64_t wcols = last ? H->ld - c0 : cols;          // the last chunk also writes the zero padding of every row
         dim3 grid((unsigned)((d + 31) / 32), (unsigned)((wcols + 31) / 32));
         hipLaunchKernelGGL(transpose_cm_to_rm_kernel, grid, dim3(256), 0, u.s_xpose, (const double*)u.staging[slot], d, d, cols,
                            H->Jd + c0, H->ld, wcols);
-        if ((e = hipGetLastError()) != hipSuccess) { bad("transpose launch", e); return; }
-        if ((e = hipEventRecord(u.freed[slot], u.s_xpose)) != hipSuccess) { bad("hipEventRecord", e); return; }
+        if ((e = hipGetLastError()) != hipSuccess) { bad("transpose launch", e); break; }
+        if ((e = hipEventRecord(u.freed[slot], u.s_xpose)) != hipSuccess) { bad("hipEventRecord", e); break; }
+        if (u.gram && !gram_step(k, u.freed[slot])) break;     // freed[slot]: recorded right behind the transpose of this chunk
     }
-    if ((e = hipStreamSynchronize(u.s_xpose)) != hipSuccess) bad("hipStreamSynchronize (upload)", e);
+    // also after an error: nothing of this upload may still be queued when the handle's buffers go
+    if ((e = hipStreamSynchronize(u.s_xpose)) != hipSuccess && u.rc == BH_OK) bad("hipStreamSynchronize (upload)", e);
+    if (u.gram && (e = hipStreamSynchronize(u.s_gram)) != hipSuccess && u.rc == BH_OK) bad("hipStreamSynchronize (Gram steps)", e);
 }
 
 // Every entry point that reads the image calls this first: joins a pending asynchronous upload (bh_hess_wait does the same).
@@ -889,6 +923,12 @@ int32_t hess_ready(bh_hess* H) {
     if (u->worker.joinable()) u->worker.join();
     const int32_t rc = u->rc;
     const std::string detail = u->detail;
+    if (u->gram && rc == BH_OK) {              // option gram_ingest: the worker has built G (its last synchronisation covered the Gram stream)
+        H->gram_builds += 1;
+        H->G_mu = u->gram_mu;
+        H->G_valid = H->mu == u->gram_mu;      // a bh_hess_set_mu during the upload: rebuilt at the next use, as ever
+    }
+    u->gram = false;
     async_upload_cleanup(u);
     H->up = nullptr;
     if (rc != BH_OK) return fail(rc, "asynchronous J upload: " + detail);
@@ -1485,6 +1525,11 @@ int32_t bh_set_option(const char* key, int64_t value) {
         while ((int64_t)g_ctx.image_pool.size() > value) { dev_free(g_ctx.image_pool.back().ptr); g_ctx.image_pool.pop_back(); }
         return BH_OK;
     }
+    if (!strcmp(key, "gram_ingest")) {
+        if (value != 0 && value != 1) return fail(BH_ERR_INVALID_ARG, "gram_ingest is 0 or 1");
+        g_ctx.opt_gram_ingest = value;
+        return BH_OK;
+    }
     if (!strcmp(key, "upload_chunk_mb")) {
         if (value < 1 || value > 4096) return fail(BH_ERR_INVALID_ARG, "upload_chunk_mb must be 1..4096");
         g_ctx.opt_upload_chunk_mb = value;
@@ -1813,6 +1858,8 @@ int32_t bh_hess_create_dev(bh_hess** out, const double* J_dev, int64_t d, int64_
     return BH_OK;
 }
 
+static int32_t gram_enter(bh_hess* H);
+
 // f-4: the same upload without blocking the caller.  J must stay valid and unchanged until bh_hess_wait (or the first use
 // of the handle, which waits implicitly) returns.
 int32_t bh_hess_create_async(bh_hess** out, const double* J, int64_t d, int64_t n, int64_t ldJ, const double* C, int64_t q,
@@ -1826,6 +1873,9 @@ int32_t bh_hess_create_async(bh_hess** out, const double* J, int64_t d, int64_t 
     bh_hess* H = new bh_hess();
     H->d = d; H->n = n; H->q = q; H->mu = mu;
     int32_t rc = alloc_hess_common(H);
+    // option gram_ingest (one rank, n <= 16384; elsewhere the call is what it is without the option): the handle is born in the Gram form
+    const bool ingest = g_ctx.opt_gram_ingest != 0 && n <= 16384 && !(comm_active() && g_ctx.nranks > 1);
+    if (rc == BH_OK && ingest) rc = gram_enter(H);
     if (rc == BH_OK) rc = upload_transposed(C, q, n, ldC, H->Jd, d, H->ld);      // the C block is small: synchronous
     if (rc == BH_OK && hipStreamSynchronize(g_ctx.stream) != hipSuccess) rc = fail(BH_ERR_HIP, "bh_hess_create_async: synchronize");
     if (rc == BH_OK && d > 0) {
@@ -1851,6 +1901,20 @@ int32_t bh_hess_create_async(bh_hess** out, const double* J, int64_t d, int64_t 
         }
         u->chunk_cols = cc;
         u->rc = BH_OK;
+        u->gram = ingest;
+        if (ok && ingest) {
+            // one more stream (with the copy, the transpose and the library stream: four) and the partial blocks of the largest step
+            u->gram_mu = mu;
+            u->gram_plan = gram_ingest_plan(H->ld, cc, (n + cc - 1) / cc, d + H->q_eff, g_ctx.n_cu);
+            if (!u->s_gram) ok = hipStreamCreateWithFlags(&u->s_gram, hipStreamNonBlocking) == hipSuccess;
+            if (ok && u->gram_part_doubles < u->gram_plan.part_doubles) {
+                dev_free(u->gram_part);
+                u->gram_part = nullptr;
+                u->gram_part_doubles = 0;
+                ok = hipMalloc(reinterpret_cast<void**>(&u->gram_part), (size_t)u->gram_plan.part_doubles * sizeof(double)) == hipSuccess;
+                if (ok) u->gram_part_doubles = u->gram_plan.part_doubles;
+            }
+        }
         if (!ok) {
             async_upload_destroy(u);
             rc = fail(BH_ERR_HIP, "bh_hess_create_async: streams / events / staging buffers");
@@ -1925,6 +1989,24 @@ static void gram_free(bh_hess* H) {
     H->G_valid = false;
 }
 
+// Into the Gram form: G and the partial sums of the one-shot build; G stale.  A failed allocation leaves the implicit form.
+static int32_t gram_enter(bh_hess* H) {
+    int slabs = 1;
+    int64_t slab_rows = 0;
+    gram_geometry(H, &slabs, &slab_rows);
+    int32_t rc = dev_alloc(&H->G, H->ld * H->ld);
+    if (rc == BH_OK && slabs > 1) rc = dev_alloc(&H->gpart, (int64_t)slabs * H->ld * H->ld);
+    if (rc != BH_OK) { gram_free(H); return rc; }        // the handle stays in the implicit form
+    H->gram_slabs = slabs;
+    H->gram_slab_rows = slab_rows;
+    H->G_valid = false;                                  // built before the first product that reads it (after the ingest)
+    H->form = BH_HESS_GRAM;
+    H->stats.bytes_per_hmul = hmul_bytes(H);
+    if (g_ctx.hw_note.H == H) g_ctx.hw_note = {};
+    if (g_ctx.gm_note.H == H) g_ctx.gm_note = {};
+    return BH_OK;
+}
+
 int32_t bh_hess_set_form(bh_hess* H, int32_t form) {
     BH_REQUIRE_INIT();
     if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
@@ -1933,23 +2015,16 @@ int32_t bh_hess_set_form(bh_hess* H, int32_t form) {
     if (form == BH_HESS_GRAM) {
         if (H->n > 16384) return fail(BH_ERR_UNSUPPORTED, "Gram form: n > 16384 (G would exceed 2 GiB)");
         if (comm_active() && g_ctx.nranks > 1) return fail(BH_ERR_UNSUPPORTED, "Gram form: one rank only (no all-reduce of G)");
-        int slabs = 1;
-        int64_t slab_rows = 0;
-        gram_geometry(H, &slabs, &slab_rows);
-        int32_t rc = dev_alloc(&H->G, H->ld * H->ld);
-        if (rc == BH_OK && slabs > 1) rc = dev_alloc(&H->gpart, (int64_t)slabs * H->ld * H->ld);
-        if (rc != BH_OK) { gram_free(H); return rc; }        // the handle stays in the implicit form
-        H->gram_slabs = slabs;
-        H->gram_slab_rows = slab_rows;
-        H->G_valid = false;                                  // built before the first product that reads it (after the ingest)
-    } else {
-        gram_free(H);
+        return gram_enter(H);
     }
+    // an upload that is building G (option gram_ingest): join the worker, which drains its Gram launches, before G goes
+    const int32_t rc = (H->up && H->up->gram) ? hess_ready(H) : BH_OK;
+    gram_free(H);
     H->form = form;
     H->stats.bytes_per_hmul = hmul_bytes(H);
     if (g_ctx.hw_note.H == H) g_ctx.hw_note = {};
     if (g_ctx.gm_note.H == H) g_ctx.gm_note = {};
-    return BH_OK;
+    return rc;
 }
 
 int32_t bh_hess_get_form(const bh_hess* H, int32_t* form, int64_t* gram_builds) {

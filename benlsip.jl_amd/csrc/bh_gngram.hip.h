@@ -23,23 +23,23 @@ namespace bh {
 // entries only), summed in slab order by gn_gram_reduce_kernel.
 constexpr int GNG_T = 256;
 constexpr int GNG_BS = 64;
-__global__ __launch_bounds__(GNG_T) void gn_gram_mfma_kernel(const double* __restrict__ J, int64_t ld, int64_t nrows, int64_t d_rows,
-                                                             double mu, int64_t slab_rows, double* __restrict__ G,
-                                                             double* __restrict__ part) {
-    __shared__ double red[2][64][64];                  // [slot][tile * 4 + reg][lane]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // packed lower block index -> (bi, bj), bi >= bj
-    const int e = blockIdx.x;
-    int bi = (int)((sqrt(8.0 * (double)e + 1.0) - 1.0) * 0.5);
+
+// packed lower block index -> (bi, bj), bi >= bj
+__device__ __forceinline__ void gn_gram_unpack(int e, int& bi, int& bj) {
+    bi = (int)((sqrt(8.0 * (double)e + 1.0) - 1.0) * 0.5);
     while ((bi + 1) * (bi + 2) / 2 <= e) ++bi;
     while (bi * (bi + 1) / 2 > e) --bi;
-    const int bj = e - bi * (bi + 1) / 2;
+    bj = e - bi * (bi + 1) / 2;
+}
+
+// The body shared by the one-shot build and the panel build of an ingest step: block (bi, bj) over the image rows [r0, r1).
+// Every thread of the workgroup calls it; true on wave 0 only, whose acc then holds the sum over the four waves.
+__device__ __forceinline__ bool gn_gram_block(const double* __restrict__ J, int64_t ld, int64_t d_rows, double mu, int bi, int bj,
+                                              int64_t r0, int64_t r1, double (*red)[64][64], dvec4 (&acc)[4][4]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t ci = (int64_t)bi * GNG_BS + 4 * (lane & 15), cj = (int64_t)bj * GNG_BS + 4 * (lane & 15);
     const bool vi = ci < ld, vj = cj < ld;             // ld is a multiple of 16: a 4-column group is all in or all out
-    const int64_t r0 = (int64_t)blockIdx.y * slab_rows;
-    const int64_t r1 = r0 + slab_rows < nrows ? r0 + slab_rows : nrows;
 
-    dvec4 acc[4][4];
 #pragma unroll
     for (int ta = 0; ta < 4; ++ta)
 #pragma unroll
@@ -86,8 +86,23 @@ __global__ __launch_bounds__(GNG_T) void gn_gram_mfma_kernel(const double* __res
     __syncthreads();
     if (wave == 1) put(0);
     __syncthreads();
-    if (wave != 0) return;
+    if (wave != 0) return false;
     add(0);
+    return true;
+}
+
+__global__ __launch_bounds__(GNG_T) void gn_gram_mfma_kernel(const double* __restrict__ J, int64_t ld, int64_t nrows, int64_t d_rows,
+                                                             double mu, int64_t slab_rows, double* __restrict__ G,
+                                                             double* __restrict__ part) {
+    __shared__ double red[2][64][64];                  // [slot][tile * 4 + reg][lane]
+    const int lane = threadIdx.x & 63;
+    int bi, bj;
+    gn_gram_unpack((int)blockIdx.x, bi, bj);
+    const int64_t r0 = (int64_t)blockIdx.y * slab_rows;
+    const int64_t r1 = r0 + slab_rows < nrows ? r0 + slab_rows : nrows;
+
+    dvec4 acc[4][4];
+    if (!gn_gram_block(J, ld, d_rows, mu, bi, bj, r0, r1, red, acc)) return;
 
     double* out = part != nullptr ? part + (int64_t)blockIdx.y * ld * ld : G;
 #pragma unroll
@@ -103,6 +118,59 @@ __global__ __launch_bounds__(GNG_T) void gn_gram_mfma_kernel(const double* __res
                 out[gr * ld + gc] = v;
                 if (part == nullptr) out[gc * ld + gr] = v;
             }
+}
+
+// Panel variant for the build that follows an asynchronous upload (option "gram_ingest", bh_gram_ingest_plan.h): the grid is
+// (the blocks of one step: packed indices block_lo + blockIdx.x) x (row slabs), so that a step of a few blocks still fills the chip.
+// part == NULL (one slab): the block goes straight into G, as above.  Else the whole 64 x 64 block of slab blockIdx.y goes to
+// part[(blockIdx.y * gridDim.x + blockIdx.x)][row in block][column in block] — a compact buffer of slabs x blocks x 4096 doubles
+// instead of slabs x ld x ld — and gn_gram_panel_reduce_kernel sums the slabs in order.
+__global__ __launch_bounds__(GNG_T) void gn_gram_panel_kernel(const double* __restrict__ J, int64_t ld, int64_t nrows, int64_t d_rows,
+                                                              double mu, int64_t slab_rows, int block_lo, double* __restrict__ G,
+                                                              double* __restrict__ part) {
+    __shared__ double red[2][64][64];
+    const int lane = threadIdx.x & 63;
+    int bi, bj;
+    gn_gram_unpack(block_lo + (int)blockIdx.x, bi, bj);
+    const int64_t r0 = (int64_t)blockIdx.y * slab_rows;
+    const int64_t r1 = r0 + slab_rows < nrows ? r0 + slab_rows : nrows;
+
+    dvec4 acc[4][4];
+    if (!gn_gram_block(J, ld, d_rows, mu, bi, bj, r0, r1, red, acc)) return;
+
+    double* pb = part != nullptr ? part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (GNG_BS * GNG_BS) : nullptr;
+#pragma unroll
+    for (int ta = 0; ta < 4; ++ta)
+#pragma unroll
+        for (int tb = 0; tb < 4; ++tb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int lr = 4 * ((lane >> 4) + 4 * r) + ta, lc = 4 * (lane & 15) + tb;
+                const double v = acc[ta][tb][r];
+                if (pb != nullptr) { pb[lr * GNG_BS + lc] = v; continue; }
+                const int64_t gr = (int64_t)bi * GNG_BS + lr, gc = (int64_t)bj * GNG_BS + lc;
+                if (gr >= ld || gc > gr) continue;
+                G[gr * ld + gc] = v;
+                G[gc * ld + gr] = v;
+            }
+}
+
+// Second stage of a panel step: entry (row, col) of every block of the step, row >= col, row < ld, is the sum over the slabs in
+// slab order; stored at (row, col) and (col, row).  One thread per entry of the nblocks x 64 x 64 panel.
+__global__ __launch_bounds__(256) void gn_gram_panel_reduce_kernel(const double* __restrict__ part, int nslabs, int nblocks, int block_lo,
+                                                                   int64_t ld, double* __restrict__ G) {
+    const int64_t total = (int64_t)nblocks * (GNG_BS * GNG_BS);
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        int bi, bj;
+        gn_gram_unpack(block_lo + (int)(idx / (GNG_BS * GNG_BS)), bi, bj);
+        const int lr = (int)(idx / GNG_BS) % GNG_BS, lc = (int)(idx % GNG_BS);
+        const int64_t gr = (int64_t)bi * GNG_BS + lr, gc = (int64_t)bj * GNG_BS + lc;
+        if (gr >= ld || gc > gr) continue;
+        double s = 0.0;
+        for (int k = 0; k < nslabs; ++k) s += part[(int64_t)k * total + idx];
+        G[gr * ld + gc] = s;
+        G[gc * ld + gr] = s;
+    }
 }
 
 // Second stage of a build split over row slabs: G[i][j] = sum over slabs, in slab order, of the lower entry (max(i,j), min(i,j)).

@@ -70,7 +70,9 @@ class AlHessian:
     @classmethod
     def create_async(cls, J, C=None, mu=0.0):
         """``bh_hess_create_async``: returns while J is still on its way to HBM (chunked copy overlapped with the device
-        transpose); ``wait()`` — or the first product — joins the upload.  The object keeps ``J`` alive until then."""
+        transpose); ``wait()`` — or the first product — joins the upload.  The object keeps ``J`` alive until then.
+        With ``set_option("gram_ingest", 1)`` (one rank, n <= 16384) the handle is born in the Gram form and ``G`` is built during
+        the upload: after ``wait()``, ``form == "gram"`` and ``gram_builds == 1``, and the first product builds nothing."""
         lib = _lib.lib()
         self = cls.__new__(cls)
         Jf = np.asfortranarray(np.asarray(J, dtype=np.float64))
@@ -490,7 +492,8 @@ def set_option(key, value):
     ``proj_form``, ``cauchy_image``, ``cauchy_gram``, ``cauchy_gram_eq`` (Cauchy search with 1..64 linear equalities from ``G`` on a
     Gram-form handle, default 0), ``gram_cg_fused`` (fused two- / three-kernel CG iteration on a Gram-form handle, default 0) and
     ``cauchy_image_refresh`` (row-space Cauchy search on one rank: R >= 1 forms the carried images again from ``J`` every R-th pass,
-    default 0 = never)."""
+    default 0 = never) and ``gram_ingest`` (``AlHessian.create_async`` builds ``G`` during the upload and returns a Gram-form handle,
+    default 0)."""
     check(_lib.lib().bh_set_option(key.encode(), int(value)), "bh_set_option(%s)" % key)
 
 

@@ -145,7 +145,15 @@ int32_t bh_hess_create_dev(bh_hess** out, const double* J_dev, int64_t d, int64_
  * (the reference evaluates the residuals and the constraints of the next point there, src/basic_tralcnlss.jl:352).
  * J must stay valid and unchanged until bh_hess_wait — or the first use of the handle, which waits implicitly — returns;
  * C is small and is copied before the call returns.  With a communicator every rank must call bh_hess_wait (or make its
- * first use of the handle) at the same point of its call sequence. */
+ * first use of the handle) at the same point of its call sequence.
+ * With option "gram_ingest" = 1 (read at this call; one rank, n <= 16384) the handle is born in the Gram form (BH_HESS_GRAM below)
+ * and G is built while J arrives: behind the transpose of every chunk the worker launches, on one more stream, the 64 x 64 lower
+ * blocks of G whose columns are all in the image by then (gn_gram_panel_kernel over row slabs + gn_gram_panel_reduce_kernel; no
+ * atomics, fixed order: G bitwise symmetric, a repeated ingest bit-identical).  When bh_hess_wait (or the implicit wait of the
+ * first use) returns, G is valid for the mu of this call, bh_hess_get_form reports BH_HESS_GRAM and one build, and the first
+ * product launches none.  A bh_hess_set_mu before that leaves G stale (rebuilt at the next use, as ever); d = 0: no upload, G
+ * comes from the C rows through the ordinary build at first use; a failed allocation of G fails the call.  bh_hess_destroy and
+ * bh_hess_set_form(H, BH_HESS_IMPLICIT) while the upload runs first wait for it and its builds. */
 int32_t bh_hess_create_async(bh_hess** out, const double* J, int64_t d, int64_t n, int64_t ldJ,
                              const double* C, int64_t q, int64_t ldC, double mu);
 int32_t bh_hess_wait(bh_hess* H);
@@ -436,6 +444,11 @@ int32_t bh_stats_reset(bh_hess* H);
  *                        once).  The reference builds a new AlHessian per accepted step and drops the old one: recycling the
  *                        2 GiB image avoids the driver's background scrub of freed VRAM and a ~4 ms hipMalloc per step.
  *   "upload_chunk_mb" [64] bh_hess_create_async: MiB of J per pipelined column chunk (1..4096)
+ *   "gram_ingest"    [0] bh_hess_create_async on one rank with n <= 16384: 1 = the handle is born in the Gram form and G is built during
+ *                        the upload, block rows of G as their columns land (see bh_hess_create_async).  Several ranks or n > 16384: the
+ *                        call is what it is with 0 (an implicit handle).  Read when the handle is created; no effect on
+ *                        bh_hess_create, bh_hess_create_dev, bh_hess_create_synthetic, bh_hess_set_form or bh_hess_set_mu.
+ *                        Values 0 / 1 (another value: BH_ERR_INVALID_ARG)
  *   "profile_stride" [8] >= 1; an event pair costs ~10 us of stream time, so 1 is for short runs only (at most 512 samples per call) */
 int32_t bh_set_option(const char* key, int64_t value);
 /* Time `reps` back-to-back launches of one kernel class with hipEvents on the launch stream.
