@@ -3,6 +3,7 @@
 // exports return once the host has what it is owed (option final_sync).
 #include "../../include/benlsip_hip.h"
 #include "bh_cauchy_plan.h"
+#include "bh_free_image_plan.h"
 #include "bh_gram_ingest_plan.h"
 #include "bh_kernels.hip.h"
 
@@ -32,6 +33,9 @@ using namespace bh;
 // Every kernel launch of the library goes through hipLaunchKernelGGL in this translation unit: count them (bh_cauchy_info reports
 // how many a search enqueued).
 static uint64_t g_kernel_launches = 0;
+// bh_proj::mask_epoch: bumped wherever fixrank of any handle is written (bh_proj_create, bh_proj_set_active,
+// bh_proj_update_active_dev, bh_cauchy_step and the renumbering behind the last two), so equal epochs name the same active set
+static uint64_t g_mask_epoch = 0;
 #undef hipLaunchKernelGGL
 #define hipLaunchKernelGGL(kernelName, ...) do { ++g_kernel_launches; hipLaunchKernelGGLInternal((kernelName), __VA_ARGS__); } while (0)
 
@@ -53,6 +57,8 @@ struct CgWorkspace {
     volatile unsigned long long* h_mirror = nullptr;   // host-mapped progress word written by the CG kernels
     unsigned long long* d_mirror = nullptr;            // its device address
     unsigned tag = 0;
+    unsigned long long* d_reroute = nullptr;           // the CG loop on the compact image of the free columns: "run this call on the full image" (bh_freeimg.hip.h)
+    unsigned long long reroute_seq = 0;                // one value per such call: the word never needs a reset
     double* d_trace = nullptr;
     int64_t trace_cap = 0;
 };
@@ -148,6 +154,7 @@ struct Ctx {
     int64_t opt_cg_fused = 1;        // box CG: two kernels per iteration (H*p with the p-update folded in + reduce/update) instead of three
     int64_t opt_proj_form = 1;       // 1: reduced mA x mA form (fast), 0: the reference's augmented mpp x mpp form
     int64_t opt_upload_chunk_mb = 64; // bh_hess_create_async: MiB of J per pipelined column chunk
+    int64_t opt_free_image = 1;      // box CG loop, one rank: stream the compact image of the free columns (0 off, 1 by the policy of bh_free_image_plan.h, 2 always)
     int64_t opt_gram_ingest = 0;     // bh_hess_create_async, one rank, n <= 16384: the handle is born in the Gram form, G built during the upload
     int64_t opt_ev_stride = 8;       // BH_FLAG_PROFILE: hipEvents around every opt_ev_stride-th H*p launch of a handle
     // RCCL
@@ -448,6 +455,17 @@ struct bh_hess {
     int64_t gram_builds = 0;
     double* geq = nullptr;         // (1 + mA) x ld: a = G D g and B = G D A' of the Cauchy search with equalities from G (lazy, grown on demand)
     int64_t geq_doubles = 0;
+    // compact image of the free columns (option free_image; bh_free_image_plan.h, bh_freeimg.hip.h)
+    double* Jf = nullptr;          // (d + q_eff) x fi.ldf row-major, from the image pool
+    int64_t Jf_doubles = 0;        // capacity of the allocation behind Jf
+    int* fi_map = nullptr;         // ld ints: slot -> original column (-1 beyond the live width)
+    int* fi_ops = nullptr;         // ld ints: the moves of one call (free_image_move_kernel)
+    std::vector<int32_t> fi_ops_h; // ... as the host planned them (kept until the next call: the upload may still be reading it)
+    FreeImageBook fi;              // host record: active set, map, width, credit, counters
+    uint64_t fi_epoch = 0;         // bh_proj::mask_epoch of the active set Jf describes (0: none)
+    double call_bytes = 0.0;       // bytes of the image the H*p launches of the running bh_pcg stream
+    double timed_bytes = 0.0;      // ... summed over the timed_n sampled launches since the last reset or change of form:
+    int64_t timed_n = 0;           //     stats.bytes_per_hmul is their mean, the bytes the sampled launches really streamed
 };
 
 struct bh_proj {
@@ -478,6 +496,7 @@ struct bh_proj {
     double* tw = nullptr;          // n + 16
     double* rpad = nullptr;        // ldA
     double* vtmp = nullptr;        // ldA
+    uint64_t mask_epoch = 0;       // a library-wide counter's value at the last write of fixrank: equal epochs mean the same active set
 };
 
 namespace {
@@ -508,6 +527,10 @@ int32_t ensure_cg_workspace(int64_t n_pad, int64_t trace_cap) {
         void* dp = nullptr;
         BH_HIP(hipHostGetDevicePointer(&dp, hp, 0));
         c.d_mirror = reinterpret_cast<unsigned long long*>(dp);
+    }
+    if (!c.d_reroute) {
+        BH_TRY(dev_alloc(&c.d_reroute, 1));
+        BH_HIP(hipMemsetAsync(c.d_reroute, 0, sizeof(unsigned long long), g_ctx.stream));
     }
     if (trace_cap > c.trace_cap) {
         dev_free(c.d_trace);
@@ -797,28 +820,41 @@ int32_t launch_jtv(bh_hess* H, const double* u_dev, double* z_out, bool with_c_r
     return reduce_slabs(H, grid, z_out, nullptr);
 }
 
+// An image of `need` doubles: from the pool when a retired one fits (>= the size needed, <= twice), else a fresh allocation.
+bool image_from_pool(int64_t need, double** ptr, int64_t* doubles) {
+    int best = -1;
+    for (int i = 0; i < (int)g_ctx.image_pool.size(); ++i) {
+        const int64_t have = g_ctx.image_pool[(size_t)i].doubles;
+        if (have >= need && have <= 2 * need && (best < 0 || have < g_ctx.image_pool[(size_t)best].doubles)) best = i;
+    }
+    if (best >= 0) {
+        *ptr = g_ctx.image_pool[(size_t)best].ptr;
+        *doubles = g_ctx.image_pool[(size_t)best].doubles;
+        g_ctx.image_pool.erase(g_ctx.image_pool.begin() + best);
+        g_ctx.image_pool_hits += 1;
+        return true;
+    }
+    return false;
+}
+int32_t image_acquire(int64_t need, double** ptr, int64_t* doubles) {
+    if (image_from_pool(need, ptr, doubles)) return BH_OK;
+    BH_TRY(dev_alloc(ptr, need));
+    *doubles = need;
+    return BH_OK;
+}
+// ... and back (the caller has drained the stream): kept for the next image when the pool has room, >= 1 MiB images only (small
+// ones are not worth a pool slot)
+void image_release(double* ptr, int64_t doubles) {
+    if (ptr && g_ctx.init && (int64_t)g_ctx.image_pool.size() < g_ctx.opt_image_pool && doubles >= (1 << 17)) g_ctx.image_pool.push_back({ptr, doubles});
+    else dev_free(ptr);
+}
+
 int32_t alloc_hess_common(bh_hess* H) {
     const int64_t rows = H->d + H->q;
     H->ld = round_up(std::max<int64_t>(H->n, 1), 16);
     H->nchunks = (int)(H->ld / 2);
     H->q_eff = (g_ctx.rank == 0) ? H->q : 0;   // C is replicated: only rank 0 contributes C'(mu C v)
-    {   // the image: from the pool when a retired one fits (>= the size needed, <= twice)
-        const int64_t need = std::max<int64_t>(rows, 1) * H->ld;
-        int best = -1;
-        for (int i = 0; i < (int)g_ctx.image_pool.size(); ++i) {
-            const int64_t have = g_ctx.image_pool[(size_t)i].doubles;
-            if (have >= need && have <= 2 * need && (best < 0 || have < g_ctx.image_pool[(size_t)best].doubles)) best = i;
-        }
-        if (best >= 0) {
-            H->Jd = g_ctx.image_pool[(size_t)best].ptr;
-            H->Jd_doubles = g_ctx.image_pool[(size_t)best].doubles;
-            g_ctx.image_pool.erase(g_ctx.image_pool.begin() + best);
-            g_ctx.image_pool_hits += 1;
-        } else {
-            BH_TRY(dev_alloc(&H->Jd, need));
-            H->Jd_doubles = need;
-        }
-    }
+    BH_TRY(image_acquire(std::max<int64_t>(rows, 1) * H->ld, &H->Jd, &H->Jd_doubles));
     BH_TRY(dev_alloc(&H->vpad, H->ld));
     BH_TRY(dev_alloc(&H->zpad, H->ld));
     BH_TRY(dev_alloc(&H->upad, std::max<int64_t>(rows, 1)));
@@ -1422,6 +1458,7 @@ int32_t bh_init(int32_t device, int32_t flags) {
     if (const char* s = getenv("BH_PROJ_FORM")) g_ctx.opt_proj_form = atoll(s) ? 1 : 0;
     if (const char* s = getenv("BH_CG_FUSED")) g_ctx.opt_cg_fused = std::min<int64_t>(std::max<int64_t>(0, atoll(s)), 2);
     if (const char* s = getenv("BH_FINAL_SYNC")) g_ctx.opt_final_sync = atoll(s) ? 1 : 0;
+    if (const char* s = getenv("BH_FREE_IMAGE")) g_ctx.opt_free_image = std::min<int64_t>(std::max<int64_t>(0, atoll(s)), 2);
     g_ctx.init = true;
     return BH_OK;
 }
@@ -1435,7 +1472,7 @@ int32_t bh_shutdown(void) {
     if (g_ctx.peer.active) peer_release(true);
     g_ctx.comm_path = 0;
     CgWorkspace& c = g_ctx.cg;
-    dev_free(c.slab); dev_free(c.d_state); dev_free(c.d_trace);
+    dev_free(c.slab); dev_free(c.d_state); dev_free(c.d_trace); dev_free(c.d_reroute);
     if (c.h_mirror) (void)hipHostFree(const_cast<unsigned long long*>(c.h_mirror));
     c = CgWorkspace();
     dev_free(g_ctx.scratch_dev); g_ctx.scratch_dev = nullptr;
@@ -1523,6 +1560,11 @@ int32_t bh_set_option(const char* key, int64_t value) {
         if (value < 0 || value > 8) return fail(BH_ERR_INVALID_ARG, "image_pool must be 0..8");
         g_ctx.opt_image_pool = value;
         while ((int64_t)g_ctx.image_pool.size() > value) { dev_free(g_ctx.image_pool.back().ptr); g_ctx.image_pool.pop_back(); }
+        return BH_OK;
+    }
+    if (!strcmp(key, "free_image")) {
+        if (value < 0 || value > 2) return fail(BH_ERR_INVALID_ARG, "free_image is 0 (off), 1 (by the policy) or 2 (build at the first eligible call)");
+        g_ctx.opt_free_image = value;
         return BH_OK;
     }
     if (!strcmp(key, "gram_ingest")) {
@@ -2002,6 +2044,7 @@ static int32_t gram_enter(bh_hess* H) {
     H->G_valid = false;                                  // built before the first product that reads it (after the ingest)
     H->form = BH_HESS_GRAM;
     H->stats.bytes_per_hmul = hmul_bytes(H);
+    H->timed_bytes = 0.0; H->timed_n = 0;
     if (g_ctx.hw_note.H == H) g_ctx.hw_note = {};
     if (g_ctx.gm_note.H == H) g_ctx.gm_note = {};
     return BH_OK;
@@ -2022,6 +2065,7 @@ int32_t bh_hess_set_form(bh_hess* H, int32_t form) {
     gram_free(H);
     H->form = form;
     H->stats.bytes_per_hmul = hmul_bytes(H);
+    H->timed_bytes = 0.0; H->timed_n = 0;
     if (g_ctx.hw_note.H == H) g_ctx.hw_note = {};
     if (g_ctx.gm_note.H == H) g_ctx.gm_note = {};
     return rc;
@@ -2031,6 +2075,49 @@ int32_t bh_hess_get_form(const bh_hess* H, int32_t* form, int64_t* gram_builds) 
     if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
     if (form) *form = H->form;
     if (gram_builds) *gram_builds = H->gram_builds;
+    return BH_OK;
+}
+
+int32_t bh_hess_free_image_info(const bh_hess* H, const bh_proj* P, int32_t* state, int64_t* width, int64_t* builds, int64_t* moves,
+                                int64_t* calls_served) {
+    if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
+    const FreeImageBook& b = H->fi;
+    int st = FI_STATE_NONE;
+    if (b.present) {
+        st = FI_STATE_VALID;
+        if (P != nullptr && H->fi_epoch != P->mask_epoch) {
+            const bool known = P->active_set && P->n == H->n && P->last_chunks.size() == (size_t)((H->n + 63) / 64);
+            st = known ? free_image_state(b, P->last_chunks.data()) : FI_STATE_STALE;
+        }
+    }
+    if (state) *state = st;
+    if (width) *width = b.present ? b.nfree : 0;
+    if (builds) *builds = b.builds;
+    if (moves) *moves = b.moves;
+    if (calls_served) *calls_served = b.served;
+    return BH_OK;
+}
+
+int32_t bh_hess_free_image_read(bh_hess* H, double* image_out, int64_t image_cap, int32_t* map_out, int64_t map_cap, int64_t* rows,
+                                int64_t* stride) {
+    BH_REQUIRE_INIT();
+    if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
+    if (!H->fi.present) return fail(BH_ERR_PRECONDITION, "bh_hess_free_image_read: the handle has no compact image");
+    const int64_t nrows = H->d + H->q_eff, ldf = H->fi.ldf;
+    if (rows) *rows = nrows;
+    if (stride) *stride = ldf;
+    if ((image_out && image_cap < nrows * ldf) || (map_out && map_cap < ldf)) return fail(BH_ERR_INVALID_ARG, "bh_hess_free_image_read: buffer too small");
+    if (image_out) {
+        count_d2h((size_t)(nrows * ldf) * sizeof(double));
+        note_dma();
+        BH_HIP(hipMemcpyAsync(image_out, H->Jf, (size_t)(nrows * ldf) * sizeof(double), hipMemcpyDeviceToHost, g_ctx.stream));
+    }
+    if (map_out) {
+        count_d2h((size_t)ldf * sizeof(int));
+        note_dma();
+        BH_HIP(hipMemcpyAsync(map_out, H->fi_map, (size_t)ldf * sizeof(int), hipMemcpyDeviceToHost, g_ctx.stream));
+    }
+    BH_TRY(sync_flush());
     return BH_OK;
 }
 
@@ -2046,11 +2133,9 @@ int32_t bh_hess_destroy(bh_hess* H) {
     }
     if (H->counted) g_ctx.live_hess -= 1;
     if (g_ctx.init) (void)hipStreamSynchronize(g_ctx.stream);
-    if (H->Jd && g_ctx.init && (int64_t)g_ctx.image_pool.size() < g_ctx.opt_image_pool && H->Jd_doubles >= (1 << 17)) {
-        g_ctx.image_pool.push_back({H->Jd, H->Jd_doubles});       // >= 1 MiB images only: small ones are not worth a pool slot
-    } else {
-        dev_free(H->Jd);
-    }
+    image_release(H->Jd, H->Jd_doubles);
+    image_release(H->Jf, H->Jf_doubles);                          // (the stream is drained: no launch still reads the compact image)
+    dev_free(H->fi_map); dev_free(H->fi_ops);
     dev_free(H->vpad); dev_free(H->zpad); dev_free(H->upad); dev_free(H->tbuf); dev_free(H->timg); dev_free(H->timg_gen);
     dev_free(H->partials); dev_free(H->sq_partials); dev_free(H->scalar);
     dev_free(H->G); dev_free(H->gpart); dev_free(H->geq);
@@ -2151,6 +2236,7 @@ int32_t bh_proj_create(bh_proj** out, const double* A, int64_t mA, int64_t n, in
     if (rc == BH_OK && hipMemsetAsync(P->fixrank, 0xff, P->ldA * sizeof(int), g_ctx.stream) != hipSuccess) rc = fail(BH_ERR_HIP, "memset");
     if (rc == BH_OK) rc = upload_transposed(A, mA, n, ldA, P->Ad, 0, P->ldA);
     if (rc != BH_OK) { bh_proj_destroy(P); return rc; }
+    P->mask_epoch = ++g_mask_epoch;
     P->nfix = 0; P->mpp = (int)mA;
     BH_TRY(sync_flush());
     *out = P;
@@ -2230,6 +2316,7 @@ int32_t bh_proj_set_active(bh_proj* P, const uint64_t* fix_chunks, int64_t n, co
         if (nfix > 0) BH_HIP(hipMemcpyAsync(P->fixidx, idx.data(), (size_t)nfix * sizeof(int), hipMemcpyHostToDevice, g_ctx.stream));
         BH_HIP(hipStreamSynchronize(g_ctx.stream));          // rank / idx are locals of this block
     }
+    P->mask_epoch = ++g_mask_epoch;
     P->nfix = nfix; P->mpp = (int)want; P->reduced = reduced;
     int info_host = 0;
     if (reduced) {
@@ -2348,11 +2435,99 @@ constexpr int kFirstBatchCap = 32;
 constexpr int kCauchyGramEqRefresh = 128;
 constexpr int kDowndateRefresh = 8;     // bh_cauchy_step, chol_downdate = 1: breakpoints between two from-scratch factorisations
 
+// ---- compact image of the free columns (option free_image) ----------------------------------
+// Jf goes back to the image pool.  (Launches that read it may be queued: the stream is drained first.)
+static void free_image_release(bh_hess* H) {
+    if (H->Jf) {
+        if (g_ctx.init) (void)hipStreamSynchronize(g_ctx.stream);
+        image_release(H->Jf, H->Jf_doubles);
+    }
+    H->Jf = nullptr; H->Jf_doubles = 0; H->fi_epoch = 0;
+    H->fi.present = false;
+}
+
+// Bytes one H*p of the CG loop streams from the compact image at its current width (hmul_bytes with n -> nfree).
+static double free_image_bytes(const bh_hess* H) {
+    return 8.0 * (double)(H->d + H->q_eff) * (double)H->fi.nfree + 16.0 * (double)H->fi.nfree;
+}
+
+// Decides, for one eligible call, whether its CG loop runs on the compact image (*use), building it or moving columns first
+// when the policy says so (bh_free_image_plan.h).  *earns: the call runs on the full image and earns credit towards a build.
+// An allocation that fails leaves the handle on the full image without an error.
+static int32_t free_image_prepare(bh_hess* H, bh_proj* P, bool* use, bool* earns) {
+    *use = false; *earns = false;
+    const int opt = (int)g_ctx.opt_free_image;
+    if (opt == 0 || P->nfix <= 0) return BH_OK;
+    FreeImageBook& b = H->fi;
+    if (b.present && H->fi_epoch == P->mask_epoch) { b.served += 1; *use = true; return BH_OK; }      // the same active set as last time
+    // the host's copy of the mask decides, and only when it is current (bh_cauchy_step leaves the device mask ahead of the host
+    // until its renumbering has come back)
+    const int64_t n = H->n;
+    const size_t nwords = (size_t)((n + 63) / 64);
+    if (!P->active_set || P->last_chunks.size() != nwords) return BH_OK;
+    const uint64_t* want = P->last_chunks.data();
+    if (free_image_count(want, n) != P->nfix) return BH_OK;
+    int64_t k_new = 0, k_freed = 0;
+    if (b.present) free_image_diff(b, want, &k_new, &k_freed);
+    const int64_t nrows = H->d + H->q_eff;
+    const FreeImageAction act = free_image_decide(opt, b.present, nrows, n, P->nfix, k_new, k_freed, b.credit, H->last_n_hmul);
+    hipStream_t s = g_ctx.stream;
+    if (act == FI_FULL) {
+        *earns = opt == 1 && !(b.present && k_freed == 0) && free_image_worthwhile(nrows, P->nfix, H->last_n_hmul);
+        return BH_OK;
+    }
+    if (act == FI_USE) { H->fi_epoch = P->mask_epoch; b.served += 1; *use = true; return BH_OK; }        // an identical mask pushed again
+    if (act == FI_MOVE) {
+        free_image_book_move(b, want, H->fi_ops_h);
+        const int k = (int)H->fi_ops_h.size();
+        count_h2d((size_t)k * sizeof(int));
+        note_dma();
+        BH_HIP(hipMemcpyAsync(H->fi_ops, H->fi_ops_h.data(), (size_t)k * sizeof(int), hipMemcpyHostToDevice, s));
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((nrows * k + 255) / 256, (int64_t)g_ctx.n_cu * 8));
+        hipLaunchKernelGGL(free_image_move_kernel, dim3(grid), dim3(256), 0, s, H->Jf, b.ldf, nrows, (int)b.nfree, k, (const int*)H->fi_ops, H->fi_map);
+        BH_HIP(hipGetLastError());
+        H->fi_epoch = P->mask_epoch; b.served += 1; *use = true;
+        return BH_OK;
+    }
+    // FI_BUILD (also: again, after a variable was freed — the image never grows)
+    free_image_release(H);
+    if (!H->fi_map) {
+        if (hipMalloc(reinterpret_cast<void**>(&H->fi_map), (size_t)H->ld * sizeof(int)) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&H->fi_ops), (size_t)H->ld * sizeof(int)) != hipSuccess) {
+            (void)hipGetLastError();
+            dev_free(H->fi_map); dev_free(H->fi_ops);
+            H->fi_map = nullptr; H->fi_ops = nullptr;
+            return BH_OK;
+        }
+    }
+    free_image_book_build(b, want, n);
+    b.present = false;                                       // until the image exists
+    const int64_t need = std::max<int64_t>(nrows, 1) * b.ldf;
+    if (!image_from_pool(need, &H->Jf, &H->Jf_doubles)) {
+        if (hipMalloc(reinterpret_cast<void**>(&H->Jf), (size_t)need * sizeof(double)) != hipSuccess) {   // out of memory: the handle stays on the full image
+            (void)hipGetLastError();
+            H->Jf = nullptr; H->Jf_doubles = 0; b.builds -= 1;
+            return BH_OK;
+        }
+        H->Jf_doubles = need;
+    }
+    b.present = true;
+    count_h2d((size_t)b.ldf * sizeof(int));
+    note_dma();
+    BH_HIP(hipMemcpyAsync(H->fi_map, b.map.data(), (size_t)b.ldf * sizeof(int), hipMemcpyHostToDevice, s));
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(nrows, (int64_t)g_ctx.n_cu * 8));
+    hipLaunchKernelGGL(free_image_build_kernel, dim3(grid), dim3(256), 0, s, (const double*)H->Jd, H->ld, nrows, (const int*)H->fi_map, H->Jf, b.ldf);
+    BH_HIP(hipGetLastError());
+    H->fi_epoch = P->mask_epoch; b.served += 1; *use = true;
+    return BH_OK;
+}
+
 // Launches the whole projected_cg on device vectors and returns once the host has seen the loop finish (the stream may
 // still hold over-launched no-op kernels).  gp/wlp/wup: n doubles readable in 16-byte chunks; wp: output.
 static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* wlp, const double* wup, double* wp, bool w_in_ws,
                        double kappa2, double atol_negcurv, double atol_f2b, int64_t trace_cap, PcgFin* fin_out, double* hw = nullptr,
-                       bool g_pad_zeroed = false /* the staged copy of g arrived with its padding already zero */) {
+                       bool g_pad_zeroed = false /* the staged copy of g arrived with its padding already zero */,
+                       bool allow_free_image = true /* false: the compact loop handed this call back (bh_freeimg.hip.h) */) {
     const int64_t n = H->n, n_pad = H->ld;
     const int64_t max_iter64 = 2 * (n - P->mA - P->nfix);   // src/basic_tralcnlss.jl:714
     if (max_iter64 < 0) return fail(BH_ERR_PRECONDITION, "n - mA - count(fixvars) < 0");
@@ -2363,6 +2538,7 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
     hipStream_t s = g_ctx.stream;
     const bool in_place = !w_in_ws;
     if (hw != nullptr) g_ctx.hw_note = {};          // cg.hw is about to be overwritten
+    H->call_bytes = hmul_bytes(H);
 
     CgArgs a{};
     a.st = c.d_state; a.w = wp; a.r = c.r; a.v = c.v; a.p = c.p; a.Hp = c.Hp; a.g = gp; a.wl = wlp; a.wu = wup;
@@ -2412,11 +2588,37 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
         H->stats.cg_kernels = (box ? 2 : (gen_linv ? 3 : 4)) + (rccl_gen ? 1 : 0);
         if (gp == c.g && n < n_pad && !g_pad_zeroed) BH_HIP(hipMemsetAsync(c.g + n, 0, (size_t)(n_pad - n) * sizeof(double), s));
         const int64_t nrows = gram ? H->ld : H->d + H->q_eff;    // Gram form: the rows of the ld x ld image of G
-        const int grid = grid_for(rs_cfg, nrows);
-        const int nblk = (H->nchunks + 15) / 16;
+        // Box constraints, one rank, implicit form, no H*w wanted: the loop may run on the compact image of the free columns (option
+        // free_image) — the same two kernels on compact operands: g, w_l, w_u gathered through the slot -> column
+        // map by one launch in front of S(1), no mask, the geometry of the compact width, and w scattered into the caller's
+        // buffer by the update kernel itself.
+        bool fi_use = false, fi_earns = false;
+        if (allow_free_image && box && !gram && !comm_active() && hw == nullptr && atol_f2b > 0) BH_TRY(free_image_prepare(H, P, &fi_use, &fi_earns));
+        const double *og = gp, *owl = wlp, *owu = wup;          // the loop's operands
+        double* ow = wp;
+        const int* ofix = a.fixrank;
+        int on = (int)n, onch = H->nchunks, ocfg = rs_cfg;
+        int64_t old = H->ld;                                    // row stride of the image and of the slabs
+        if (fi_use) {
+            const FreeImageBook& b = H->fi;
+            og = c.x; owl = c.xlow; owu = c.xupp; ow = c.s;     // (staging vectors of bh_minor_iterate: free during a bh_pcg)
+            ofix = nullptr;
+            on = (int)b.nfree; onch = (int)(round_up(b.nfree, 16) / 2); ocfg = pick_config(onch);
+            old = b.ldf;                                        // (after a move the live width is smaller than the stride)
+            H->call_bytes = free_image_bytes(H);
+            c.reroute_seq += 1;
+            FreeGatherArgs ga{};
+            ga.g = gp; ga.wl = wlp; ga.wu = wup; ga.fixrank = P->fixrank; ga.map = H->fi_map;
+            ga.gc = c.x; ga.wlc = c.xlow; ga.wuc = c.xupp; ga.wc = c.s; ga.w = wp;
+            ga.n = (int)n; ga.n_pad = (int)n_pad; ga.nfree = on;
+            ga.reroute = c.d_reroute; ga.seq = c.reroute_seq; ga.mirror = a.mirror; ga.tag = a.tag;
+            hipLaunchKernelGGL(free_image_gather_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, s, ga);
+        }
+        const int grid = grid_for(ocfg, nrows);
+        const int nblk = (onch + 15) / 16;
         double* pbuf[2] = {c.p, c.p2};
         double* rvbuf[2] = {c.rvpart, c.rvpart + n_pad / 2};
-        const int nch_v = gen_linv ? H->nchunks : ((int)n + 1) / 2;    // proj_apply_linv_kernel also keeps the padding of v at zero
+        const int nch_v = gen_linv ? H->nchunks : (on + 1) / 2;       // proj_apply_linv_kernel also keeps the padding of v at zero
         const int nrv = fuse_gen ? (nch_v + 63) / 64 : nblk;            // who writes the r.v partials: the projection kernel (64 chunks per workgroup) or the update kernel
         const int vv_off = (int)(n_pad / 4);                            // v.v partials of the init launch, behind the r.v partials (nrv <= n_pad / 128)
         if (gen_linv) {
@@ -2442,13 +2644,15 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
             RowStreamArgs ra = rs_args(H, nrows, nullptr);
             ra.partials = H->partials;
             if (gram) { ra.J = H->G; ra.d_rows = nrows; ra.mu = 1.0; ra.partials = nullptr; ra.t_out = c.Hp; }     // H*p leaves as one vector
+            if (fi_use) { ra.J = H->Jf; ra.ld = old; ra.nchunks = onch; }
             if (fuse_gen) { ra.v = c.p; ra.negate = 0; }                            // used by j == 1 only: p_1 = -P(g), formed by the init kernels
-            else { ra.v = gp; ra.negate = 1; ra.negmask = a.fixrank; }             //                      p_1 = -mask(g), formed on the fly
+            else { ra.v = og; ra.negate = 1; ra.negmask = ofix; }                  //                      p_1 = -mask(g), formed on the fly
             CgFuse& f = ra.cf;
-            f.st = c.d_state; f.j = j; f.n = (int)n; f.max_iter = max_iter; f.init_done = gen_linv ? 2 : fuse_gen ? 1 : 0; f.vv_off = vv_off;
+            f.st = c.d_state; f.j = j; f.n = on; f.max_iter = max_iter; f.init_done = gen_linv ? 2 : fuse_gen ? 1 : 0; f.vv_off = vv_off;
             f.vvec = c.v; f.p_old = pbuf[(j - 1) & 1]; f.p_new = pbuf[j & 1];
             f.rvpart = rvbuf[(j - 1) & 1]; f.nrv = nrv;
-            f.w = wp; f.wl = wlp; f.wu = wup;
+            f.w = ow; f.wl = owl; f.wu = owu;
+            if (fi_use) { f.reroute = c.d_reroute; f.reroute_seq = c.reroute_seq; }
             f.sqpart = H->sq_partials; f.gpart = H->sq_partials + H->g_cap;      // one entry per WORKGROUP (up to g_cap of them), not per chunk
             f.kappa2 = kappa2; f.atol_f2b = atol_f2b;
             f.trace = a.trace; f.trace_cap = a.trace_cap; f.mirror = a.mirror; f.tag = a.tag;
@@ -2458,16 +2662,17 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
             // a handle without history cannot predict its exit: its look-ahead launches (j > 1) take the no-prefetch symbol too, so
             // that launches which stop in their prologue never show up under the streaming kernel's name in a profile
             if (gram) launch_gram_cg(rs_cfg, ra, grid, s, expect_stop);
-            else launch_row_stream_cgp(rs_cfg, ra, grid, s, expect_stop);
+            else launch_row_stream_cgp(ocfg, ra, grid, s, expect_stop);
             if (slot >= 0) BH_HIP(hipEventRecord(H->ev[2 * slot + 1], s));
             return BH_OK;
         };
         auto launch_update = [&](int j) -> int32_t {
             CgUpdArgs u{};
-            u.st = c.d_state; u.j = j; u.partials = H->partials; u.ld = H->ld; u.nchunks = H->nchunks; u.G = grid; u.Gs = grid; u.Gq = grid;
+            u.st = c.d_state; u.j = j; u.partials = H->partials; u.ld = old; u.nchunks = onch; u.G = grid; u.Gs = grid; u.Gq = grid;
             u.sqpart = H->sq_partials; u.gpart = H->sq_partials + H->g_cap; u.rvpart_in = rvbuf[(j - 1) & 1]; u.rvpart_out = rvbuf[j & 1]; u.nrv = nrv;
-            u.p = pbuf[j & 1]; u.w = wp; u.hw = hw; u.r = c.r; u.g = gp; u.v = c.v; u.fixrank = a.fixrank;
-            u.n = (int)n; u.atol_neg = atol_negcurv; u.trace = a.trace; u.trace_cap = a.trace_cap; u.mirror = a.mirror; u.tag = a.tag;
+            u.p = pbuf[j & 1]; u.w = ow; u.hw = hw; u.r = c.r; u.g = og; u.v = c.v; u.fixrank = ofix;
+            if (fi_use) { u.map = H->fi_map; u.w_full = wp; u.reroute = c.d_reroute; u.reroute_seq = c.reroute_seq; }
+            u.n = on; u.atol_neg = atol_negcurv; u.trace = a.trace; u.trace_cap = a.trace_cap; u.mirror = a.mirror; u.tag = a.tag;
             // Gram form: ONE "slab", the finished G p; the partials of dot(p, H*p) and of gamma stay one per workgroup of the G·v grid
             // (up to n_cu * kMaxBlocksPerCu of them: LaneBatch holds the first 512 in registers and folds the rest in index order)
             if (gram) { u.partials = c.Hp; u.Gs = 1; }
@@ -2555,6 +2760,12 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
         }
         BH_TRY(wait_mirror(c, a.tag, kNever, &mw));          // the final state
         if (!mw.done) return fail(BH_ERR_HIP, "internal: CG loop did not terminate");
+        if (fi_use && mw.status == kCgReroute) {
+            // a non-finite g on a fixed variable: the full image decides (every compact launch still queued returns at once)
+            H->fi.served -= 1;
+            return pcg_run(H, P, gp, wlp, wup, wp, w_in_ws, kappa2, atol_negcurv, atol_f2b, trace_cap, fin_out, hw, g_pad_zeroed, false);
+        }
+        if (fi_earns) H->fi.credit += free_image_saving(mw.n_hmul, P->nfix, n);
         fin_out->done = mw.done; fin_out->status = mw.status; fin_out->iter = mw.iter; fin_out->n_hmul = mw.n_hmul;
         fin_out->results_final = (mw.status == BH_CG_SOLVED || mw.status == BH_CG_MAX_ITER_REACHED || mw.status == BH_CG_NONE);
         fin_out->tag = a.tag;
@@ -2748,8 +2959,11 @@ static int32_t pcg_finish(bh_hess* H, const PcgFin& fin, bool drained = true) {
             if (hipEventElapsedTime(&ms, H->ev[2 * i], H->ev[2 * i + 1]) == hipSuccess) {
                 H->stats.hmul_ms += ms;
                 H->stats.hmul_timed += 1;
+                H->timed_bytes += H->call_bytes;
+                H->timed_n += 1;
             }
         }
+        if (H->timed_n > 0) H->stats.bytes_per_hmul = H->timed_bytes / (double)H->timed_n;
         H->ev_pending.clear();
     }
     return BH_OK;
@@ -3092,6 +3306,7 @@ int32_t bh_proj_update_active_dev(bh_proj* P, const double* x_dev, const double*
     const bool had_factor = P->active_set && P->reduced && P->M_valid;   // M and Lr describe the CURRENT active set: a downdate is enough
     hipLaunchKernelGGL(active_update_kernel, dim3(1), dim3(CG_T), 0, s, x_dev, s_dev, xlow_dev, xupp_dev, delta, atol, (int)P->n, (int)P->ldA,
                        mA, P->fixrank, P->newidx, P->counts);
+    P->mask_epoch = ++g_mask_epoch;
     BH_HIP(hipGetLastError());
     int counts[4] = {0, 0, 0, 0};
     if (mA > 0) {
@@ -3216,6 +3431,7 @@ static int32_t adopt_device_mask(bh_proj* P, uint64_t* fix_chunks_out, int* info
         BH_TRY(sync_flush());
     }
     P->nfix = counts[AU_FIXED]; P->mpp = (int)P->mA + P->nfix; P->reduced = P->mA > 0; P->have_L = false;
+    P->mask_epoch = ++g_mask_epoch;
     P->last_chunks = chunks;
     P->active_set = true;
     if (fix_chunks_out) memcpy(fix_chunks_out, chunks.data(), nwords * sizeof(uint64_t));
@@ -3599,6 +3815,7 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     run.img_cap = (std::max<int64_t>(H->d + H->q, 1) + 1) / 2 * 2;
     BH_TRY(cauchy_ensure_buffers(run));
     P->active_set = false;             // device mask is authoritative until adopt_mask below
+    P->mask_epoch = ++g_mask_epoch;
     hipLaunchKernelGGL(cauchy_init_kernel, dim3(1), dim3(CG_T), 0, s, a);
     if (mA > 0) BH_TRY(launch_reduced_factor(P, true, nullptr));
     const int max_pass = plan.max_pass;
@@ -3731,6 +3948,7 @@ int32_t bh_stats_reset(bh_hess* H) {
     const double b = H->stats.bytes_per_hmul;
     H->stats = bh_stats_t{};
     H->stats.bytes_per_hmul = b;
+    H->timed_bytes = 0.0; H->timed_n = 0;
     H->hmul_seq = 0;          // the first H*p after a reset is always sampled (BH_FLAG_PROFILE)
     return BH_OK;
 }
@@ -3804,10 +4022,15 @@ int32_t bh_time_kernel(bh_hess* H, int32_t kind, int32_t reps, double* avg_ms) {
         return BH_OK;
     }
     if (multi_panel(H)) return fail(BH_ERR_UNSUPPORTED, "bh_time_kernel: single-panel handles only (n <= 16384)");
-    const int cfg = pick_config(H->nchunks);
+    int cfg = pick_config(H->nchunks);
     RowStreamArgs a{};
     a.J = H->Jd; a.ld = H->ld; a.d_rows = H->d; a.nchunks = H->nchunks; a.mu = H->mu; a.state = nullptr;
     a.v = H->vpad; a.u = H->upad; a.partials = H->partials;
+    if (kind == 0 && H->fi.present && g_ctx.opt_free_image != 0) {
+        // the image the handle's H*p launches stream now: the compact one, at its live width
+        a.J = H->Jf; a.ld = H->fi.ldf; a.nchunks = (int)(round_up(H->fi.nfree, 16) / 2);
+        cfg = pick_config(a.nchunks);
+    }
     a.nrows = (kind == 0) ? H->d + H->q_eff : H->d;
     a.t_out = (kind == 1) ? H->upad : nullptr;
     const int mode = kind == 0 ? MODE_FUSED : (kind == 1 ? MODE_JV : MODE_JTV);

@@ -47,6 +47,10 @@ struct CgUpdArgs {
     const double* A; int64_t ldA; int mA;
     double* tpart;                  // [gridDim.x][mA]
     int init_in_memory;             // j == 1: r = g and w = 0 are already in memory (init kernels), not taken from g
+    // Loop on the compact image of the free columns (bh_freeimg.hip.h): every vector above is compact; w also reaches the caller's
+    // buffer through the slot -> column map, from the same thread that updates it (NULL: the vectors are the caller's own)
+    const int* map; double* w_full;
+    const unsigned long long* reroute; unsigned long long reroute_seq;      // as CgFuse::reroute
 };
 
 // grid = ceil(nchunks / 16) workgroups of 256 threads = 16 chunks x 16 slab lanes (as reduce_partials_kernel).
@@ -57,6 +61,7 @@ template <bool GEN, bool PEER>
 __global__ __launch_bounds__(256) void cg_reduce_update_kernel(CgUpdArgs a, PeerArgs pa) {
     CgState* st = a.st;
     if (st->stop_at != 0 && a.j > st->stop_at) return;
+    if (a.reroute != nullptr && *a.reroute == a.reroute_seq) return;
     __shared__ double2 sm[16][17];
     __shared__ double rvs[16];
     __shared__ double2 rsm[16];                  // GEN: the masked new r of this workgroup's 16 chunks
@@ -103,6 +108,8 @@ __global__ __launch_bounds__(256) void cg_reduce_update_kernel(CgUpdArgs a, Peer
 #pragma unroll
         for (int k = 0; k < 4; ++k) arow[k] = A2[(int64_t)min(rl + 16 * k, a.mA - 1) * ldA2 + cc];
     }
+    int2 mp = make_int2(-1, -1);
+    if (!GEN && upd && a.map != nullptr) mp = reinterpret_cast<const int2*>(a.map)[c];      // (the compact loop has no equalities)
     if (upd && a.fixrank != nullptr) fr = reinterpret_cast<const int2*>(a.fixrank)[c];   // last: its compare is scheduled next to it
 
     // ---- this workgroup's 32 columns of Hp = sum of the slabs (fixed order) --------------------------------------------
@@ -220,6 +227,8 @@ __global__ __launch_bounds__(256) void cg_reduce_update_kernel(CgUpdArgs a, Peer
         if (add_w || a.j == 1) {
             reinterpret_cast<double2*>(a.w)[c] = wk;
             if (a.hw != nullptr) reinterpret_cast<double2*>(a.hw)[c] = hwk;
+            if (!GEN && mp.x >= 0) a.w_full[mp.x] = wk.x;            // (slots at or beyond the live width map to -1)
+            if (!GEN && mp.y >= 0) a.w_full[mp.y] = wk.y;
         }
         if (cont || a.j == 1) {
             reinterpret_cast<double2*>(a.r)[c] = rk;

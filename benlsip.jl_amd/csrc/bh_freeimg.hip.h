@@ -1,0 +1,104 @@
+// bh_freeimg.hip.h — the compact image of the free columns (option "free_image"): build, column moves, and the gather in front
+// of the box-constrained CG loop that runs on it
+// Part of the single translation unit of bh_api.hip (see bh_kernels.hip.h for the layout and design notes).
+//
+// In the box-constrained CG loop every p_j is zero on the fixed variables, and their entries of H*p are used for nothing
+// (src/basic_tralcnlss.jl:729-745: w += step p and r.v never see them).  Jf holds one row per row of the image of J and only
+// the columns of the free variables, dense, row stride ldf: a sweep over it reads (n - nfix) / n of the bytes.  The policy is in
+// bh_free_image_plan.h, the driver in pcg_run (bh_api.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "bh_reduce.hip.h"
+
+namespace bh {
+
+// Jf[row][c'] = J[row][map[c']] for c' < ldf (map[c'] < 0: zero padding).  One workgroup per row at a time, 16-byte stores;
+// a pair of slots that maps to an aligned pair of neighbouring columns is read with one 16-byte load.
+__global__ __launch_bounds__(256) void free_image_build_kernel(const double* __restrict__ J, int64_t ld, int64_t nrows,
+                                                               const int* __restrict__ map, double* __restrict__ Jf, int64_t ldf) {
+    const int nch = (int)(ldf >> 1);
+    for (int64_t row = blockIdx.x; row < nrows; row += gridDim.x) {
+        const double* __restrict__ src = J + row * ld;
+        double2* __restrict__ dst = reinterpret_cast<double2*>(Jf + row * ldf);
+        for (int c = threadIdx.x; c < nch; c += 256) {
+            const int2 m = reinterpret_cast<const int2*>(map)[c];
+            double2 x = make_double2(0.0, 0.0);
+            if (m.x >= 0 && m.y == m.x + 1 && (m.x & 1) == 0) {
+                const dvec2 t = __builtin_nontemporal_load(reinterpret_cast<const dvec2*>(src + m.x));
+                x = make_double2(t.x, t.y);
+            } else {
+                if (m.x >= 0) x.x = __builtin_nontemporal_load(src + m.x);
+                if (m.y >= 0) x.y = __builtin_nontemporal_load(src + m.y);
+            }
+            dst[c] = x;
+        }
+    }
+}
+
+// The moves of one call: the old columns t in [nfree_new, nfree_new + k) leave the image.  dst_of_tail[t - nfree_new] >= 0: column
+// t goes to that slot (a slot below nfree_new whose variable became fixed); either way column t is zero afterwards.  One thread
+// per (row, t); no slot is both read and written (bh_free_image_plan.h).  Workgroup 0 also carries the slot -> column map along.
+__global__ __launch_bounds__(256) void free_image_move_kernel(double* __restrict__ Jf, int64_t ldf, int64_t nrows, int nfree_new, int k,
+                                                              const int* __restrict__ dst_of_tail, int* __restrict__ map) {
+    const int64_t total = nrows * (int64_t)k;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int64_t row = idx / k;
+        const int t = (int)(idx - row * k);
+        const int dst = dst_of_tail[t];
+        double* __restrict__ rp = Jf + row * ldf;
+        const double x = rp[nfree_new + t];
+        if (dst >= 0) rp[dst] = x;
+        rp[nfree_new + t] = 0.0;
+    }
+    if (blockIdx.x == 0) {
+        for (int t = threadIdx.x; t < k; t += 256) {
+            const int dst = dst_of_tail[t];
+            const int var = map[nfree_new + t];
+            if (dst >= 0) map[dst] = var;
+            map[nfree_new + t] = -1;
+        }
+    }
+}
+
+// The one launch in front of the CG loop on the compact image: g, w_l, w_u gathered through the map (zero beyond nfree, up to
+// n_pad), the caller's w zeroed on the fixed variables (the loop only ever writes the free ones).  A non-finite g on a FIXED
+// variable makes r.v NaN in the loop on the full image (r = g there, NaN * 0); the compact loop never sees that entry, so such a
+// call is handed back: `seq` goes into *reroute (every kernel of this call's compact loop then returns at once) and the
+// progress word reports done with status kCgReroute, on which the host runs the call on the full image.
+constexpr int kCgReroute = 15;
+struct FreeGatherArgs {
+    const double* g; const double* wl; const double* wu;      // n
+    const int* fixrank;                                       // >= 0: fixed
+    const int* map;                                           // ldf
+    double* gc; double* wlc; double* wuc;                     // n_pad each
+    double* wc;                                               // n_pad: the compact w (zeroed here)
+    double* w;                                                // n: the caller's w
+    int n, n_pad, nfree;
+    unsigned long long* reroute; unsigned long long seq;
+    unsigned long long* mirror; unsigned tag;
+};
+
+__global__ __launch_bounds__(256) void free_image_gather_kernel(FreeGatherArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < a.n_pad) {
+        const int m = (i < a.nfree) ? a.map[i] : -1;
+        a.gc[i] = (m >= 0) ? a.g[m] : 0.0;
+        a.wlc[i] = (m >= 0) ? a.wl[m] : 0.0;
+        a.wuc[i] = (m >= 0) ? a.wu[m] : 0.0;
+        a.wc[i] = 0.0;
+    }
+    if (i < a.n && a.fixrank[i] >= 0) {
+        a.w[i] = 0.0;
+        const double gi = a.g[i];
+        if (!(fabs(gi) <= 1.7976931348623157e308)) {          // NaN or +-Inf
+            *a.reroute = a.seq;
+            if (a.mirror != nullptr) {
+                const unsigned long long wv = ((unsigned long long)(a.tag & 0xffffu) << 48) | ((unsigned long long)kCgReroute << 44) | (1ull << 40);
+                __hip_atomic_store(a.mirror, wv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+    }
+}
+
+}  // namespace bh

@@ -28,3 +28,4 @@
 #include "bh_minor.hip.h"
 #include "bh_gngram.hip.h"
 #include "bh_gramcg.hip.h"
+#include "bh_freeimg.hip.h"

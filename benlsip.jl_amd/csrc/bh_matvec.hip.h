@@ -51,6 +51,9 @@ struct CgFuse {
     const double* g;        // j == 1: r_1 = g_minor (:705)
     const int* fixrank;     // v = mask(r)
     double atol_neg;
+    // CGP = 1, 2 on the compact image of the free columns (bh_freeimg.hip.h): the gather in front of the loop stores `reroute_seq`
+    // here when the call has to run on the full image instead — every launch of the compact loop then returns at once (NULL: not used)
+    const unsigned long long* reroute; unsigned long long reroute_seq;
 };
 
 struct RowStreamArgs {
@@ -92,6 +95,7 @@ __global__ __launch_bounds__(T) void row_stream_kernel(RowStreamArgs a) {
     // the loop stopped before this iteration (CGP = 3: the launch that FINDS the stop is j = stop_at + 1 and writes stop_at itself —
     // every one of its workgroups must still get through its prologue, whose owner stores complete w)
     if (CGP && a.cf.j > 1 && a.cf.st->stop_at != 0 && a.cf.j > a.cf.st->stop_at + (CGP == 3 ? 1 : 0)) return;
+    if ((CGP == 1 || CGP == 2) && a.cf.reroute != nullptr && *a.cf.reroute == a.cf.reroute_seq) return;
     constexpr int NW = T / 64;
     __shared__ double red[2][R][NW];
     __shared__ double pro[2][NW];                                       // CGP, iteration 1, workgroup 0 only

@@ -196,6 +196,28 @@ class AlHessian:
         check(_lib.lib().bh_time_kernel(self._h, kind, reps, ct.byref(ms)), "bh_time_kernel")
         return ms.value
 
+    _FREE_IMAGE_STATES = {0: "none", 1: "valid", 2: "stale"}
+
+    def free_image_info(self, lincons=None):
+        """``bh_hess_free_image_info``: what the handle holds of the compact image of the free columns (option ``free_image``) —
+        ``state`` ("none", "valid", or "stale" against the current active set of ``lincons``), ``width``, ``builds``, ``moves``
+        (columns) and ``calls_served``."""
+        st, w, b, m, c = ct.c_int32(0), ct.c_int64(0), ct.c_int64(0), ct.c_int64(0), ct.c_int64(0)
+        check(_lib.lib().bh_hess_free_image_info(self._h, None if lincons is None else lincons.handle, ct.byref(st), ct.byref(w),
+                                                 ct.byref(b), ct.byref(m), ct.byref(c)), "bh_hess_free_image_info")
+        return {"state": self._FREE_IMAGE_STATES[st.value], "width": w.value, "builds": b.value, "moves": m.value, "calls_served": c.value}
+
+    def free_image_read(self):
+        """``bh_hess_free_image_read`` (debugging): ``(image, map)`` — the compact image as it lies in memory (rows x stride) and
+        its slot -> original column map (-1 from the live width on)."""
+        rows, stride = ct.c_int64(0), ct.c_int64(0)
+        check(_lib.lib().bh_hess_free_image_read(self._h, None, 0, None, 0, ct.byref(rows), ct.byref(stride)), "bh_hess_free_image_read")
+        img = np.empty((rows.value, stride.value))
+        mp = np.empty(stride.value, dtype=np.int32)
+        check(_lib.lib().bh_hess_free_image_read(self._h, ptr(img), img.size, ptr(mp), mp.size, ct.byref(rows), ct.byref(stride)),
+              "bh_hess_free_image_read")
+        return img, mp
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             _lib.lib().bh_hess_destroy(self._h)

@@ -74,7 +74,9 @@ typedef struct bh_stats_t {
     int64_t n_allreduce;     /* RCCL all-reduces issued                                  */
     double  hmul_ms;         /* sum of hipEvent durations of the H*p kernel (BH_FLAG_PROFILE) */
     int64_t hmul_timed;      /* number of H*p launches contributing to hmul_ms           */
-    double  bytes_per_hmul;  /* algorithmic bytes of one H*p launch on this rank (8*(d+q)*n + 16*n) */
+    double  bytes_per_hmul;  /* algorithmic bytes of one H*p launch on this rank (8*(d+q)*n + 16*n); once launches have been
+                              * sampled (hmul_timed > 0): the mean over those launches of the bytes of the image each one
+                              * streamed — 8*(d+q)*nfree + 16*nfree for a launch on the compact image of option "free_image" */
     /* library-wide (all handles), since bh_init: host <-> device copies the library has issued — vectors staged for the
      * host-pointer entry points, masks, factors, traces, J uploads; 8-byte scalars coming back through pinned memory are
      * included.  The *_dev entry points move none of the n-vectors they work on (tests check the difference of these counters). */
@@ -191,6 +193,19 @@ int32_t bh_hess_destroy(bh_hess* H);
 int32_t bh_hess_set_form(bh_hess* H, int32_t form);
 int32_t bh_hess_get_form(const bh_hess* H, int32_t* form, int64_t* gram_builds);
 int32_t bh_hess_shape(const bh_hess* H, int64_t* d, int64_t* n, int64_t* q);
+/* The compact image of the free columns (option "free_image"): one row per row of the image of J, only the columns of the
+ * variables that are free, dense; the box-constrained CG loop of bh_pcg* streams it instead of J.
+ * bh_hess_free_image_info: state = 0 none, 1 valid, 2 stale — with `lincons` given: an image exists but describes another
+ * active set than the current one of `lincons` (newly fixed variables are moved out by the next eligible call when that pays;
+ * a freed variable needs a rebuild); with NULL an existing image reports 1.  width = its live columns (0: none), builds and
+ * moves (columns) = since the handle was created, calls_served = bh_pcg* calls whose CG loop ran on it.  Any pointer may be NULL.
+ * bh_hess_free_image_read (debugging and tests): the image as it lies in memory, rows x stride doubles row-major (columns from
+ * width on are zero), and the slot -> original column map (stride ints, -1 from width on).  rows / stride are always reported;
+ * a NULL buffer is skipped; BH_ERR_PRECONDITION when the handle has no image, BH_ERR_INVALID_ARG when a buffer is too small. */
+int32_t bh_hess_free_image_info(const bh_hess* H, const bh_proj* lincons, int32_t* state, int64_t* width, int64_t* builds, int64_t* moves,
+                                int64_t* calls_served);
+int32_t bh_hess_free_image_read(bh_hess* H, double* image_out, int64_t image_cap, int32_t* map_out, int64_t map_cap, int64_t* rows,
+                                int64_t* stride);
 
 /* Base.:*(H::AlHessian, v) — src/basic_tralcnlss.jl:102-106:  out = J'(Jv) + C'(mu C v). */
 int32_t bh_hmul(bh_hess* H, const double* v, double* out_n);
@@ -444,6 +459,21 @@ int32_t bh_stats_reset(bh_hess* H);
  *                        once).  The reference builds a new AlHessian per accepted step and drops the old one: recycling the
  *                        2 GiB image avoids the driver's background scrub of freed VRAM and a ~4 ms hipMalloc per step.
  *   "upload_chunk_mb" [64] bh_hess_create_async: MiB of J per pipelined column chunk (1..4096)
+ *   "free_image"     [1] bh_pcg*, box constraints (no linear equalities) on one rank, implicit form, two-kernel iteration ("cg_fused"),
+ *                        n <= 16384, atol_f2b > 0: the CG loop streams a compact image of the FREE columns of J instead of J — every p_j is
+ *                        zero on the fixed variables and their entries of H*p are used for nothing, so nfix / n of every sweep is saved.
+ *                        The image belongs to the handle ((d + q) x (n - nfix) doubles from the image pool) and follows an active set
+ *                        that grows by moving single columns; a freed variable makes it stale until it is built again.
+ *                        1 = by a policy: every eligible call earns n_hmul * nfix / n sweeps of credit, the image is built at the start
+ *                        of the next eligible call once the credit has reached the cost of a build, and newly fixed variables are moved
+ *                        out when that costs less than the saving predicted from the previous call (else that call streams J);
+ *                        2 = built at the first eligible call, moves always applied (tests, A/B runs); 0 = off.  A failed allocation
+ *                        leaves the handle on the full image without an error.  status, iters, n_hmul, the trace and the tie log keep
+ *                        their meaning; w is exactly 0 on the fixed variables; p'Hp and r.v are summed in the order of the compact
+ *                        columns (another rounding than on the full image).  A non-finite g on a fixed variable: the call runs on the
+ *                        full image.  bh_minor_iterate* (it wants H*w), linear equalities, several ranks and the Gram form are never
+ *                        eligible.  bh_hess_free_image_info reports what the handle holds.  Another value: BH_ERR_INVALID_ARG.
+ *                        (The environment variable BH_FREE_IMAGE, read by bh_init, sets the initial value.)
  *   "gram_ingest"    [0] bh_hess_create_async on one rank with n <= 16384: 1 = the handle is born in the Gram form and G is built during
  *                        the upload, block rows of G as their columns land (see bh_hess_create_async).  Several ranks or n > 16384: the
  *                        call is what it is with 0 (an implicit handle).  Read when the handle is created; no effect on
@@ -452,7 +482,8 @@ int32_t bh_stats_reset(bh_hess* H);
  *   "profile_stride" [8] >= 1; an event pair costs ~10 us of stream time, so 1 is for short runs only (at most 512 samples per call) */
 int32_t bh_set_option(const char* key, int64_t value);
 /* Time `reps` back-to-back launches of one kernel class with hipEvents on the launch stream.
- * kind: 0 = fused J'(Jp), 1 = J·v, 2 = J'·u; 3..6 = read-only stream probe over the same image (nothing but 16-byte
+ * kind: 0 = fused J'(Jp) over the image the handle's CG loop streams now (the compact image of option "free_image" once the handle
+ * holds one, else J), 1 = J·v, 2 = J'·u; 3..6 = read-only stream probe over the same image (nothing but 16-byte
  * non-temporal loads and adds) with 1, 2, 4, 8 workgroups per CU: the practical single-read ceiling the kernels are
  * quoted against; 7 = the all-reduce of one n-vector on the active communicator path (every rank must call it together);
  * 8 = everything an H*p does after its streaming kernel (slab reduction + all-reduce; without a communicator: the slab

@@ -11,6 +11,9 @@ OUT=$R/gpurun_out/prof_$TAG
 rm -rf $OUT
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
+# the compact image of the free columns from the first call on (the policy would build it some calls into the run: the per-kernel
+# averages below would then mix launches over the full and over the compact image)
+export BH_FREE_IMAGE=${BH_FREE_IMAGE:-2}
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --full --no-cpu-baseline --no-ic-extra $EXTRA > $OUT/trace.log 2>&1
 grep '^{' $OUT/trace.log > $OUT/bench_line_under_trace.json || true
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -- python3 $R/bench.py --full --no-cpu-baseline --no-extras --steps 5 --warmup 1 --preheat 0 $EXTRA > $OUT/fetch.log 2>&1
