@@ -6,6 +6,8 @@
 #include "bh_free_image_plan.h"
 #include "bh_gram_ingest_plan.h"
 #include "bh_kernels.hip.h"
+#include "bh_launch_ahead.h"
+#include "bh_pcg_plan.h"
 
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -541,7 +543,6 @@ int32_t ensure_cg_workspace(int64_t n_pad, int64_t trace_cap) {
     return BH_OK;
 }
 
-struct MirrorWord { int done, status, iter, n_hmul; };
 int32_t check_peer_error();
 int32_t hess_ready(bh_hess* H);
 
@@ -2414,6 +2415,24 @@ int32_t bh_left_mul_tr(bh_proj* P, const double* y, double* out_n) {
 // point then returns without draining the stream: what is still in flight are prologue-only launches that write nothing.
 struct PcgFin { int done, status, iter, n_hmul; bool results_final = false; unsigned tag = 0; };
 
+static void pcg_fin_fill(PcgFin* fin, const MirrorWord& mw, unsigned tag, bool results_final) {
+    fin->done = mw.done; fin->status = mw.status; fin->iter = mw.iter; fin->n_hmul = mw.n_hmul;
+    fin->results_final = results_final; fin->tag = tag;
+}
+
+// The tag of the next loop on the progress word (16 bits, never 0).
+static unsigned next_mirror_tag(CgWorkspace& c) {
+    c.tag = (c.tag + 1) & 0xffffu;
+    if (c.tag == 0) c.tag = 1;
+    return c.tag;
+}
+
+// g doubles as an H*p input: stale padding of its staged copy would be multiplied into the dot products.
+static int32_t zero_staged_g_padding(CgWorkspace& c, const double* gp, int64_t n, int64_t n_pad, bool g_pad_zeroed) {
+    if (gp == c.g && n < n_pad && !g_pad_zeroed) BH_HIP(hipMemsetAsync(c.g + n, 0, (size_t)(n_pad - n) * sizeof(double), g_ctx.stream));
+    return BH_OK;
+}
+
 // How many iterations the host enqueues per launch-ahead batch.  One batch is always in flight while the host waits for
 // the one before it, so the GPU never idles as long as the host can enqueue a batch faster than the GPU runs one; every
 // iteration enqueued past the exit is a gated no-op that still costs ~1.5 us per kernel (measured, tools/dispatch_floor.py)
@@ -2427,13 +2446,6 @@ static int launch_batch_size(const bh_hess* H) {
     const double est_us = (multi_panel(H) ? 16.0 : 8.0) * rows * (double)H->n / 7.0e6;      // ~7 TB/s streaming rate
     return est_us >= 100.0 ? 1 : est_us >= 40.0 ? 2 : 4;
 }
-// The first batch is sized by the previous call on the handle (consecutive subproblems of a minor loop behave alike):
-// an exact prediction means no gated launches and no host round trip inside the loop at all.
-constexpr int kFirstBatchCap = 32;
-// bh_cauchy_step, option cauchy_gram_eq: passes between two formations of a = G D g, B = G D A' from the device-side mask
-// (the smallest power of two at which a formation costs at most 5 % of the passes in between: DESIGN.md §8 f-5)
-constexpr int kCauchyGramEqRefresh = 128;
-constexpr int kDowndateRefresh = 8;     // bh_cauchy_step, chol_downdate = 1: breakpoints between two from-scratch factorisations
 
 // ---- compact image of the free columns (option free_image) ----------------------------------
 // Jf goes back to the image pool.  (Launches that read it may be queued: the stream is drained first.)
@@ -2522,8 +2534,324 @@ static int32_t free_image_prepare(bh_hess* H, bh_proj* P, bool* use, bool* earns
     return BH_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// projected_cg: the plan of one call (decided once), its run context, one launcher pair per shape
+// ------------------------------------------------------------------------------------------
+struct PcgPlan {
+    PcgSelection sel{};             // the shape and its flags (bh_pcg_plan.h)
+    bool gram = false;              // the loop streams G instead of J
+    int max_iter = 0;
+    int64_t nrows = 0;              // rows of the image the H*p launch streams
+    int cfg = -1, grid = 1;         // row-stream geometry and its grid (fused shape on the compact image: of the compact width)
+    int nblk = 1;                   // workgroups of the update / slab-reduction kernel
+    int nch_v = 0;                  // chunks of v the projection kernel forms
+    int nrv = 1;                    // who writes the r.v partials: the projection kernel (64 chunks per workgroup) or the update kernel
+    int vv_off = 0;                 // v.v partials of the init launch, behind the r.v partials (nrv <= n_pad / 128)
+    double* pbuf[2] = {nullptr, nullptr};    // ping-pong: p ...
+    double* rvbuf[2] = {nullptr, nullptr};   // ... the r.v partials (fused shape)
+    double* rbuf[2] = {nullptr, nullptr};    // ... r and the gamma partials, one per workgroup (box shape over RCCL)
+    double* gbuf[2] = {nullptr, nullptr};
+    LaunchAhead sched{};            // the launch-ahead schedule (bh_launch_ahead.h)
+};
+
+// What the launches of one call share.
+struct PcgRun {
+    bh_hess* H;
+    bh_proj* P;
+    CgWorkspace& c;
+    hipStream_t s;
+    CgArgs a{};
+    PcgPlan plan;
+    double* wp = nullptr;           // the caller's w
+    double* hw = nullptr;
+    // the loop's operands: the caller's, or their compact twins (free_image)
+    const double *og = nullptr, *owl = nullptr, *owu = nullptr;
+    double* ow = nullptr;
+    const int* ofix = nullptr;
+    int on = 0, onch = 0;
+    int64_t old = 0;                // row stride of the image and of the slabs
+    bool fi_use = false;            // the loop runs on the compact image of the free columns
+    int expect_stop_at = 0;         // the launch expected to find the loop finished
+};
+
+// Geometry of the fused shape for a loop over `nch` chunks of `n_loop` variables.
+static void pcg_fused_geometry(PcgPlan& p, const bh_hess* H, int nch, int n_loop) {
+    p.cfg = pick_config(nch);
+    p.grid = grid_for(p.cfg, p.nrows);
+    p.nblk = (nch + 15) / 16;
+    p.nch_v = p.sel.gen_linv ? H->nchunks : (n_loop + 1) / 2;       // proj_apply_linv_kernel also keeps the padding of v at zero
+    p.nrv = p.sel.fuse_gen ? (p.nch_v + 63) / 64 : p.nblk;
+}
+
+// Decides everything about the call from the handles and the options.  Launches and allocates nothing.
+static PcgPlan pcg_make_plan(const bh_hess* H, const bh_proj* P, int max_iter, bool g_padded, bool hw_wanted, double atol_f2b,
+                             bool allow_free_image) {
+    const CgWorkspace& c = g_ctx.cg;
+    const int64_t n = H->n, n_pad = H->ld;
+    PcgPlan p;
+    p.gram = H->form == BH_HESS_GRAM;
+    p.max_iter = max_iter;
+    const int rs_cfg = multi_panel(H) ? -1 : pick_config(H->nchunks);
+    PcgSelectIn in{};
+    in.mA = P->mA; in.gram_handle = p.gram;
+    in.cg_fused = g_ctx.opt_cg_fused; in.gram_cg_fused = g_ctx.opt_gram_cg_fused; in.linv_refine = g_ctx.opt_linv_refine; in.fold_init = g_ctx.opt_fold_init;
+    in.comm = comm_active(); in.peer_path = use_peer_path();
+    in.reduced = P->reduced; in.tpart = P->tpart != nullptr; in.W = P->W != nullptr; in.M_valid = P->M_valid; in.lda_is_ld = P->ldA == H->ld;
+    in.rs_cfg_ok = rs_cfg >= 0; in.cgp3_ok = rs_cfg >= 0 && cgp3_supported(rs_cfg); in.peer_blocks_fit = (H->nchunks + 15) / 16 <= kPeerBlkCap;
+    in.iterates = max_iter >= 1; in.g_padded = g_padded; in.vectors_in_regs = (n + 1) / 2 <= 4 * CG_T;
+    in.hw_wanted = hw_wanted; in.atol_f2b_positive = atol_f2b > 0; in.allow_free_image = allow_free_image;
+    p.sel = pcg_select(in);
+    const int batch = launch_batch_size(H);
+    const bool rccl_path = comm_active() && !use_peer_path();
+    // (an RCCL all-reduce cannot be gated from the device: every over-launched iteration pays for one.  With history on the handle
+    // the first batch is the previous call's count exactly, so a repeated subproblem enqueues as many collectives as it has H*p
+    // products; without history it stays small.)
+    int cold = std::min(batch, rccl_path ? 1 : 2);
+    p.sched.max_units = max_iter; p.sched.batch = batch; p.sched.off = 0; p.sched.look_first = true;
+    p.sched.await_iter = false; p.sched.lock_step = true;           // (bh_launch_ahead.h: the lock-step rule)
+    p.pbuf[0] = c.p; p.pbuf[1] = c.p2;
+    if (p.sel.shape == PCG_FUSED) {
+        p.nrows = p.gram ? H->ld : H->d + H->q_eff;                 // Gram form: the rows of the ld x ld image of G
+        pcg_fused_geometry(p, H, H->nchunks, (int)n);
+        p.vv_off = (int)(n_pad / 4);
+        p.rvbuf[0] = c.rvpart; p.rvbuf[1] = c.rvpart + n_pad / 2;
+        // S(j + 1) speaks for iteration j: either "stopped" (done) or "iter = j + 1, streaming".  Every iteration of the RCCL form
+        // holds a collective; the peer-buffer exchange sits inside a kernel that a gated launch skips.
+        p.sched.await_iter = true; p.sched.lock_step = p.sel.rccl_gen;
+        cold = p.sel.rccl_gen ? 1 : std::min(batch, 2);
+    } else if (p.sel.shape == PCG_RCCL_BOX) {
+        p.nrows = H->d + H->q_eff;
+        p.cfg = rs_cfg; p.grid = grid_for(rs_cfg, p.nrows); p.nblk = (H->nchunks + 15) / 16;
+        p.rbuf[0] = c.r; p.rbuf[1] = c.r2;
+        p.gbuf[0] = H->sq_partials + H->g_cap; p.gbuf[1] = H->sq_partials + 2 * (int64_t)H->g_cap;
+        cold = 1;
+    }
+    p.sched.first = launch_ahead_first(H->last_n_hmul, cold);
+    return p;
+}
+
+// The loop moves to the compact image of the free columns: compact operands (staging vectors of bh_minor_iterate: free during a
+// bh_pcg), no mask, the geometry of the compact width.
+static void pcg_use_free_image(PcgRun& r) {
+    bh_hess* H = r.H; CgWorkspace& c = r.c;
+    const FreeImageBook& b = H->fi;
+    r.fi_use = true;
+    r.og = c.x; r.owl = c.xlow; r.owu = c.xupp; r.ow = c.s;
+    r.ofix = nullptr;
+    r.on = (int)b.nfree; r.onch = (int)(round_up(b.nfree, 16) / 2);
+    r.old = b.ldf;                                            // (after a move the live width is smaller than the stride)
+    pcg_fused_geometry(r.plan, H, r.onch, r.on);
+    H->call_bytes = free_image_bytes(H);
+    c.reroute_seq += 1;
+}
+
+// ---- fused shape: S(1) | U(1) S(2) | U(2) S(3) | ...  The stream kernel of iteration j+1 is what detects "solved" after
+// iteration j, so it is always enqueued together with U(j) (as a gated no-op if the loop ended in U(j)).
+static int32_t pcg_fused_stream(PcgRun& r, int j) {             // H*p of iteration j (1-based), p_j formed on the fly
+    bh_hess* H = r.H; CgWorkspace& c = r.c; const PcgPlan& p = r.plan;
+    RowStreamArgs ra = rs_args(H, p.nrows, nullptr);
+    ra.partials = H->partials;
+    if (p.gram) { ra.J = H->G; ra.d_rows = p.nrows; ra.mu = 1.0; ra.partials = nullptr; ra.t_out = c.Hp; }     // H*p leaves as one vector
+    if (r.fi_use) { ra.J = H->Jf; ra.ld = r.old; ra.nchunks = r.onch; }
+    if (p.sel.fuse_gen) { ra.v = c.p; ra.negate = 0; }                            // used by j == 1 only: p_1 = -P(g), formed by the init kernels
+    else { ra.v = r.og; ra.negate = 1; ra.negmask = r.ofix; }                    //                      p_1 = -mask(g), formed on the fly
+    CgFuse& f = ra.cf;
+    f.st = c.d_state; f.j = j; f.n = r.on; f.max_iter = p.max_iter; f.init_done = p.sel.gen_linv ? 2 : p.sel.fuse_gen ? 1 : 0; f.vv_off = p.vv_off;
+    f.vvec = c.v; f.p_old = p.pbuf[(j - 1) & 1]; f.p_new = p.pbuf[j & 1];
+    f.rvpart = p.rvbuf[(j - 1) & 1]; f.nrv = p.nrv;
+    f.w = r.ow; f.wl = r.owl; f.wu = r.owu;
+    if (r.fi_use) { f.reroute = c.d_reroute; f.reroute_seq = c.reroute_seq; }
+    f.sqpart = H->sq_partials; f.gpart = H->sq_partials + H->g_cap;      // one entry per WORKGROUP (up to g_cap of them), not per chunk
+    f.kappa2 = r.a.kappa2; f.atol_f2b = r.a.atol_f2b;
+    f.trace = r.a.trace; f.trace_cap = r.a.trace_cap; f.mirror = r.a.mirror; f.tag = r.a.tag;
+    int slot = -1;
+    const bool expect_stop = j == r.expect_stop_at || j > p.max_iter || (r.expect_stop_at == 0 && j > 1);
+    BH_TRY(profile_begin(H, j - 1, &slot));
+    // a handle without history cannot predict its exit: its look-ahead launches (j > 1) take the no-prefetch symbol too, so
+    // that launches which stop in their prologue never show up under the streaming kernel's name in a profile
+    if (p.gram) launch_gram_cg(p.cfg, ra, p.grid, r.s, expect_stop);
+    else launch_row_stream_cgp(p.cfg, ra, p.grid, r.s, expect_stop);
+    if (slot >= 0) BH_HIP(hipEventRecord(H->ev[2 * slot + 1], r.s));
+    return BH_OK;
+}
+
+static int32_t pcg_fused_update(PcgRun& r, int j) {
+    bh_hess* H = r.H; bh_proj* P = r.P; CgWorkspace& c = r.c; const PcgPlan& p = r.plan; hipStream_t s = r.s;
+    const int nblk = p.nblk, grid = p.grid;
+    CgUpdArgs u{};
+    u.st = c.d_state; u.j = j; u.partials = H->partials; u.ld = r.old; u.nchunks = r.onch; u.G = grid; u.Gs = grid; u.Gq = grid;
+    u.sqpart = H->sq_partials; u.gpart = H->sq_partials + H->g_cap; u.rvpart_in = p.rvbuf[(j - 1) & 1]; u.rvpart_out = p.rvbuf[j & 1]; u.nrv = p.nrv;
+    u.p = p.pbuf[j & 1]; u.w = r.ow; u.hw = r.hw; u.r = c.r; u.g = r.og; u.v = c.v; u.fixrank = r.ofix;
+    if (r.fi_use) { u.map = H->fi_map; u.w_full = r.wp; u.reroute = c.d_reroute; u.reroute_seq = c.reroute_seq; }
+    u.n = r.on; u.atol_neg = r.a.atol_neg; u.trace = r.a.trace; u.trace_cap = r.a.trace_cap; u.mirror = r.a.mirror; u.tag = r.a.tag;
+    // Gram form: ONE "slab", the finished G p; the partials of dot(p, H*p) and of gamma stay one per workgroup of the G·v grid
+    // (up to n_cu * kMaxBlocksPerCu of them: LaneBatch holds the first 512 in registers and folds the rest in index order)
+    if (p.gram) { u.partials = c.Hp; u.Gs = 1; }
+    if (!p.sel.fuse_gen) {
+        if (p.sel.peer_fused) hipLaunchKernelGGL((cg_reduce_update_kernel<false, true>), dim3(nblk), dim3(256), 0, s, u, g_ctx.peer.args);
+        else hipLaunchKernelGGL((cg_reduce_update_kernel<false, false>), dim3(nblk), dim3(256), 0, s, u, PeerArgs{});
+        return BH_OK;
+    }
+    if (p.sel.rccl_gen) {
+        // the collective is enqueued by the host between the slab reduction (which packs this rank's share of p'Hp behind the
+        // vector) and the update kernel, which then sums ONE slab — the all-reduced H*p
+        const int n_pad = r.a.n_pad;
+        hipLaunchKernelGGL(reduce_partials_sq_kernel, dim3(nblk), dim3(256), 0, s, (const double*)H->partials, H->ld, H->nchunks, grid,
+                           c.hpx, (const double*)H->sq_partials, n_pad, (const CgState*)c.d_state, j);
+        BH_HIP(hipGetLastError());
+        BH_TRY(allreduce_inplace(c.hpx, (int64_t)n_pad + 2, H));
+        u.partials = c.hpx; u.Gs = 1; u.sqpart = c.hpx + n_pad; u.Gq = 1;
+    }
+    // (A, L and the vectors are replicated: past the exchange every rank forms the same partials of A_free r, the same v)
+    u.A = P->Ad; u.ldA = P->ldA; u.mA = (int)P->mA; u.tpart = P->tpart; u.init_in_memory = p.sel.gen_linv ? 0 : 1;
+    if (p.sel.peer_fused) hipLaunchKernelGGL((cg_reduce_update_kernel<true, true>), dim3(nblk), dim3(256), 0, s, u, g_ctx.peer.args);
+    else hipLaunchKernelGGL((cg_reduce_update_kernel<true, false>), dim3(nblk), dim3(256), 0, s, u, PeerArgs{});
+    // y = (A_free A_free')^{-1} (A_free r): partial sums + the two triangular solves; then v = r_free - A_free'y and r.v
+    ProjArgs pa = proj_args(P, c.d_state, true);
+    pa.tpart = P->tpart; pa.tpart_nblk = nblk; pa.rvpart = p.rvbuf[j & 1]; pa.fused_j = j;
+    if (p.sel.gen_linv) {
+        pa.W = P->W; pa.nch_pad = H->nchunks; pa.Mgram = p.sel.linv_refine ? P->M : nullptr;
+        hipLaunchKernelGGL((proj_apply_linv_kernel<false>), dim3((unsigned)p.nrv), dim3(256), 0, s, pa, (const double*)c.r, c.v);
+        return BH_OK;
+    }
+    hipLaunchKernelGGL(trsv_small_kernel, dim3(1), dim3(256), 0, s, pa);
+    hipLaunchKernelGGL((proj_left_mul_tr_kernel<true, 4>), dim3((p.nch_v + 63) / 64), dim3(256), 0, s, pa, (const double*)c.r, c.v);
+    return BH_OK;
+}
+
+static int32_t pcg_fused_first(PcgRun& r) {
+    bh_hess* H = r.H; bh_proj* P = r.P; CgWorkspace& c = r.c; const PcgPlan& p = r.plan; hipStream_t s = r.s;
+    if (r.fi_use) {
+        // g, w_l, w_u gathered through the slot -> column map by one launch in front of S(1); w is scattered into the caller's
+        // buffer by the update kernel itself
+        FreeGatherArgs ga{};
+        ga.g = r.a.g; ga.wl = r.a.wl; ga.wu = r.a.wu; ga.fixrank = P->fixrank; ga.map = H->fi_map;
+        ga.gc = c.x; ga.wlc = c.xlow; ga.wuc = c.xupp; ga.wc = c.s; ga.w = r.wp;
+        ga.n = r.a.n; ga.n_pad = r.a.n_pad; ga.nfree = r.on;
+        ga.reroute = c.d_reroute; ga.seq = c.reroute_seq; ga.mirror = r.a.mirror; ga.tag = r.a.tag;
+        hipLaunchKernelGGL(free_image_gather_kernel, dim3((unsigned)((r.a.n_pad + 255) / 256)), dim3(256), 0, s, ga);
+    }
+    if (p.sel.gen_linv) {
+        if (!P->linv_valid) {
+            hipLaunchKernelGGL(tri_inv_small_kernel, dim3(1), dim3(256), 0, s, (const double*)P->Lr, (int)P->mA, P->W);
+            P->linv_valid = true;
+        }
+        // :705-710 in two launches: tw = A_free mask(g); v = P(g), p_1 = -v and the partials of r.v, v.v.  r = g and w = 0 are
+        // formed by the first update kernel, CgState is set by workgroup 0 of the first H*p launch (init_done = 2).
+        ProjArgs pa = proj_args(P, nullptr, true);
+        hipLaunchKernelGGL(proj_left_mul_kernel, dim3((unsigned)P->mA), dim3(256), 0, s, pa, r.a.g);
+        pa.tpart = P->tw; pa.tpart_nblk = 1; pa.rvpart = p.rvbuf[0]; pa.vvpart = p.rvbuf[0] + p.vv_off; pa.p_out = c.p;
+        pa.W = P->W; pa.nch_pad = H->nchunks; pa.Mgram = p.sel.linv_refine ? P->M : nullptr; pa.fused_j = 0;
+        hipLaunchKernelGGL((proj_apply_linv_kernel<true>), dim3((unsigned)p.nrv), dim3(256), 0, s, pa, r.a.g, c.v);
+    } else if (p.sel.fuse_gen) {
+        // :702-718 by the init kernels: r = g, w = 0, v = P(r), rtv, p_1 = -v (in c.p), tol_cg, CgState (stop_at = 0)
+        hipLaunchKernelGGL((cg_init_kernel<false>), dim3(1), dim3(CG_T), 0, s, r.a);
+        BH_TRY(launch_project(P, c.r, c.v, c.d_state));
+        hipLaunchKernelGGL(cg_init_finish_kernel, dim3(1), dim3(CG_T), 0, s, r.a);
+    }
+    return pcg_fused_stream(r, 1);
+}
+
+static int32_t pcg_fused_unit(PcgRun& r, int index) {              // index = j - 1: U(j), S(j + 1)
+    BH_TRY(pcg_fused_update(r, index + 1));
+    BH_TRY(pcg_fused_stream(r, index + 2));                         // (iteration max_iter + 1 only ever runs its prologue: iter > max_iter)
+    BH_HIP(hipGetLastError());
+    return BH_OK;
+}
+
+// ---- box constraints over RCCL: TWO kernels and the collective per iteration.  An ncclAllReduce is enqueued by
+// the host, so it cannot sit inside the update kernel as the peer-buffer exchange does; instead the update of iteration j-1 moves
+// into the prologue of the H*p launch of iteration j (row_stream_kernel<..., CGP = 3>: every workgroup redoes it for the whole
+// 32 KiB vector, the owners of a chunk store it), and the slab reduction packs this rank's share of p'Hp behind the vector that
+// goes through the all-reduce:  S(1) | R(1) AR(1) S(2) | R(2) AR(2) S(3) | ...
+static int32_t pcg_rccl_box_stream(PcgRun& r, int j) {
+    bh_hess* H = r.H; CgWorkspace& c = r.c; const PcgPlan& p = r.plan; const CgArgs& a = r.a;
+    RowStreamArgs ra = rs_args(H, p.nrows, nullptr);
+    ra.partials = H->partials;
+    ra.v = a.g; ra.negate = 1; ra.negmask = a.fixrank;                // j == 1: p_1 = -mask(g), formed on the fly
+    CgFuse& f = ra.cf;
+    f.st = c.d_state; f.j = j; f.n = a.n; f.max_iter = p.max_iter; f.init_done = 0;
+    f.p_old = p.pbuf[(j - 1) & 1]; f.p_new = p.pbuf[j & 1];
+    f.r_old = p.rbuf[(j - 1) & 1]; f.r_new = p.rbuf[j & 1];
+    f.gpart_in = p.gbuf[(j - 1) & 1]; f.gpart = p.gbuf[j & 1];
+    f.w_rw = r.wp; f.w = r.wp; f.hw = r.hw; f.g = a.g; f.fixrank = a.fixrank;
+    f.wl = a.wl; f.wu = a.wu;
+    f.sqpart = H->sq_partials;
+    f.Hp = c.hpx; f.sq_index = a.n_pad;
+    f.kappa2 = a.kappa2; f.atol_f2b = a.atol_f2b; f.atol_neg = a.atol_neg;
+    f.trace = a.trace; f.trace_cap = a.trace_cap; f.mirror = a.mirror; f.tag = a.tag;
+    int slot = -1;
+    BH_TRY(profile_begin(H, j - 1, &slot));
+    launch_row_stream_cgp3(p.cfg, ra, p.grid, r.s);
+    if (slot >= 0) BH_HIP(hipEventRecord(H->ev[2 * slot + 1], r.s));
+    return BH_OK;
+}
+
+static int32_t pcg_rccl_box_unit(PcgRun& r, int index) {           // index = j - 1: R(j), AR(j), S(j + 1)
+    bh_hess* H = r.H; CgWorkspace& c = r.c; const PcgPlan& p = r.plan;
+    const int j = index + 1;
+    hipLaunchKernelGGL(reduce_partials_sq_kernel, dim3(p.nblk), dim3(256), 0, r.s, (const double*)H->partials, H->ld, H->nchunks, p.grid,
+                       c.hpx, (const double*)H->sq_partials, r.a.n_pad, (const CgState*)c.d_state, j);
+    BH_HIP(hipGetLastError());
+    BH_TRY(allreduce_inplace(c.hpx, (int64_t)r.a.n_pad + 2, H));
+    return pcg_rccl_box_stream(r, j + 1);
+}
+
+// ---- separate-kernel shape.  Kernels of iterations past the exit see state->done and return at once.
+static int32_t pcg_separate_first(PcgRun& r) {
+    const bool box = r.P->mA == 0;
+    // fold_init: no init kernel — the first H*p forms p0 = -mask(g) on the fly and the first step kernel does the initialisation
+    // of :702-718 itself
+    if (!r.plan.sel.fold_init && box) {
+        hipLaunchKernelGGL((cg_init_kernel<true>), dim3(1), dim3(CG_T), 0, r.s, r.a);
+    } else if (!r.plan.sel.fold_init) {
+        hipLaunchKernelGGL((cg_init_kernel<false>), dim3(1), dim3(CG_T), 0, r.s, r.a);
+        BH_TRY(launch_project(r.P, r.c.r, r.c.v, r.c.d_state));
+        hipLaunchKernelGGL(cg_init_finish_kernel, dim3(1), dim3(CG_T), 0, r.s, r.a);
+    }
+    BH_HIP(hipGetLastError());
+    return BH_OK;
+}
+
+static int32_t pcg_separate_unit(PcgRun& r, int index) {
+    bh_hess* H = r.H; CgWorkspace& c = r.c;
+    if (r.plan.sel.fold_init && index == 0) {
+        // the state still holds the previous call's `done`: this launch is never a no-op, so it is not gated
+        BH_TRY(launch_hmul(H, r.a.g, c.Hp, nullptr, index, true, r.a.fixrank));                    // :722 with p = -P(g)
+        launch_cg_first_step(r.a, r.s);
+        return BH_OK;
+    }
+    BH_TRY(launch_hmul(H, c.p, c.Hp, c.d_state, index));   // :722
+    if (r.P->mA == 0) {
+        launch_cg_step<0>(r.a, r.s);
+    } else {
+        launch_cg_step<1>(r.a, r.s);
+        BH_TRY(launch_project(r.P, c.r, c.v, c.d_state));            // :741
+        launch_cg_step<2>(r.a, r.s);
+    }
+    return BH_OK;
+}
+
+// What goes out in front of the loop (the init launches, S(1) of the shapes that have one) ...
+static int32_t pcg_launch_first(PcgRun& r) {
+    switch (r.plan.sel.shape) {
+        case PCG_FUSED: return pcg_fused_first(r);
+        case PCG_RCCL_BOX: return pcg_rccl_box_stream(r, 1);
+        default: return pcg_separate_first(r);
+    }
+}
+// ... and launch unit `index` of the schedule: iteration index + 1.
+static int32_t pcg_launch_unit(PcgRun& r, int index) {
+    switch (r.plan.sel.shape) {
+        case PCG_FUSED: return pcg_fused_unit(r, index);
+        case PCG_RCCL_BOX: return pcg_rccl_box_unit(r, index);
+        default: return pcg_separate_unit(r, index);
+    }
+}
+
 // Launches the whole projected_cg on device vectors and returns once the host has seen the loop finish (the stream may
 // still hold over-launched no-op kernels).  gp/wlp/wup: n doubles readable in 16-byte chunks; wp: output.
+// Which shape runs: pcg_make_plan (the rule: bh_pcg_plan.h); the launch schedule and its lock-step rule: bh_launch_ahead.h.
 static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* wlp, const double* wup, double* wp, bool w_in_ws,
                        double kappa2, double atol_negcurv, double atol_f2b, int64_t trace_cap, PcgFin* fin_out, double* hw = nullptr,
                        bool g_pad_zeroed = false /* the staged copy of g arrived with its padding already zero */,
@@ -2532,401 +2860,53 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
     const int64_t max_iter64 = 2 * (n - P->mA - P->nfix);   // src/basic_tralcnlss.jl:714
     if (max_iter64 < 0) return fail(BH_ERR_PRECONDITION, "n - mA - count(fixvars) < 0");
     if (max_iter64 >= 0xfffff) return fail(BH_ERR_UNSUPPORTED, "2*(n - mA - count(fixvars)) exceeds the 20-bit iteration counters of the progress word");
-    const int max_iter = (int)max_iter64;
     CgWorkspace& c = g_ctx.cg;
     H->ev_pending.clear();
-    hipStream_t s = g_ctx.stream;
-    const bool in_place = !w_in_ws;
     if (hw != nullptr) g_ctx.hw_note = {};          // cg.hw is about to be overwritten
     H->call_bytes = hmul_bytes(H);
 
-    CgArgs a{};
+    PcgRun run{H, P, c, g_ctx.stream};
+    CgArgs& a = run.a;
     a.st = c.d_state; a.w = wp; a.r = c.r; a.v = c.v; a.p = c.p; a.Hp = c.Hp; a.g = gp; a.wl = wlp; a.wu = wup;
     a.fixrank = P->nfix > 0 ? P->fixrank : nullptr;
-    a.n = (int)n; a.n_pad = (int)n_pad; a.w_in_ws = in_place ? 0 : 1; a.max_iter = max_iter; a.kappa2 = kappa2; a.atol_neg = atol_negcurv; a.atol_f2b = atol_f2b;
+    a.n = (int)n; a.n_pad = (int)n_pad; a.w_in_ws = w_in_ws ? 1 : 0; a.max_iter = (int)max_iter64; a.kappa2 = kappa2; a.atol_neg = atol_negcurv; a.atol_f2b = atol_f2b;
     a.trace = trace_cap > 0 ? c.d_trace : nullptr; a.trace_cap = (int)std::min<int64_t>(trace_cap, 0x7fffffff);
-    c.tag = (c.tag + 1) & 0xffffu;
-    if (c.tag == 0) c.tag = 1;
-    a.mirror = c.d_mirror; a.tag = c.tag;
+    a.mirror = c.d_mirror; a.tag = next_mirror_tag(c);
     a.hw = hw;
+    run.wp = wp; run.hw = hw;
+    run.og = gp; run.owl = wlp; run.owu = wup; run.ow = wp; run.ofix = a.fixrank;
+    run.on = (int)n; run.onch = H->nchunks; run.old = H->ld;
+    run.expect_stop_at = H->last_n_hmul > 0 ? H->last_n_hmul + 1 : 0;
 
-    const bool box = (P->mA == 0);
-    // Box constraints, one rank, J rows register-resident: TWO kernels per iteration instead of three (bh_cgfuse.hip.h) — the
-    // H*p launch forms p on the fly and takes the exit test, one 128-workgroup kernel reduces the slabs and updates w, r, v.
-    // (g doubles as the first H*p input, so it must be readable up to the padded length: workspace copy or n == ld.)
-    const int rs_cfg = multi_panel(H) ? -1 : pick_config(H->nchunks);
-    // General constraints in the reduced projection form with mA <= 64 get the same treatment.
-    // Default (cg_fused = 1): THREE kernels instead of seven — H*p (p formed on the fly), reduce/update leaving partials of A_free r,
-    // and proj_apply_linv_kernel, whose every workgroup sums those partials and applies the explicit inverse of the factor
-    // (tri_inv_small_kernel, rebuilt only when the factor changed: two 64-term dot products per entry instead of the
-    // single-workgroup 128-step triangular solve) before forming its chunks of v = P(r) and its partial of r.v.
-    // cg_fused = 2: FOUR kernels — the triangular solves in a launch of their own (trsv_small_kernel summing the partials),
-    // then left_mul_tr.  Both change pHp's rounding like the box form does (cg_fused = 0 keeps dot(p, H*p)).
-    // Gram form: the fused shapes are opt-in through an option of their own (gram_cg_fused, independent of cg_fused; a Gram handle is
-    // single-rank by construction) and exist in the two- and the three-kernel form only — gram_cg_kernel streams G instead of J
-    // and leaves H*p as one finished vector with the partials of dot(p, H*p) (bh_gramcg.hip.h); everything else takes the
-    // separate-kernel shape below, as every Gram handle does without the option.
-    const bool gram = H->form == BH_HESS_GRAM;
-    const int64_t cg_fused = !gram ? g_ctx.opt_cg_fused : (g_ctx.opt_gram_cg_fused != 0 && !comm_active()) ? 1 : 0;
-    const bool fuse_gen = !box && cg_fused >= 1 && P->reduced && P->mA <= 64 && P->tpart != nullptr && P->ldA == H->ld &&
-                          (!gram || P->W != nullptr);
-    const bool gen_linv = fuse_gen && cg_fused == 1 && P->W != nullptr;
-    // (one equality: the "factor" is a scalar, y = t / l^2 has no conditioning to repair — the refinement step would only move the last bit)
-    const bool linv_refine = gen_linv && g_ctx.opt_linv_refine != 0 && P->M_valid && P->mA >= 2;
-    // Several ranks: the two-kernel (equalities: three-kernel) form carries the exchange inside the update kernel when the
-    // peer-buffer transport is the active one (cg_reduce_update_kernel<GEN, true>: push the workgroup's 32 columns + its rank's share of pHp, wait, sum in
-    // rank order); an RCCL all-reduce cannot sit inside a kernel, so that path keeps the three-kernel form.
-    const bool peer_fused = comm_active() && use_peer_path() && (box || fuse_gen) && (H->nchunks + 15) / 16 <= kPeerBlkCap;
-    // Equalities over RCCL: the collective is enqueued by the host between the slab reduction (which packs this rank's share of
-    // p'Hp behind the vector, as in the box form below) and the update kernel, which then sums ONE slab — the all-reduced H*p:
-    //   S(1) | R(1) AR(1) U(1) P(1) S(2) | ...   four kernels + the collective instead of seven, on the lock-step launch schedule.
-    const bool rccl_gen = comm_active() && !use_peer_path() && fuse_gen;
-    if ((box || fuse_gen) && cg_fused && rs_cfg >= 0 && (!comm_active() || peer_fused || rccl_gen) && max_iter >= 1 &&
-        (gp == c.g || n == n_pad)) {
-        BH_TRY(hess_ready(H));
-        if (gram) BH_TRY(ensure_gram(H));                  // G rebuilt first when stale, on the same stream
-        H->stats.cg_kernels = (box ? 2 : (gen_linv ? 3 : 4)) + (rccl_gen ? 1 : 0);
-        if (gp == c.g && n < n_pad && !g_pad_zeroed) BH_HIP(hipMemsetAsync(c.g + n, 0, (size_t)(n_pad - n) * sizeof(double), s));
-        const int64_t nrows = gram ? H->ld : H->d + H->q_eff;    // Gram form: the rows of the ld x ld image of G
-        // Box constraints, one rank, implicit form, no H*w wanted: the loop may run on the compact image of the free columns (option
-        // free_image) — the same two kernels on compact operands: g, w_l, w_u gathered through the slot -> column
-        // map by one launch in front of S(1), no mask, the geometry of the compact width, and w scattered into the caller's
-        // buffer by the update kernel itself.
-        bool fi_use = false, fi_earns = false;
-        if (allow_free_image && box && !gram && !comm_active() && hw == nullptr && atol_f2b > 0) BH_TRY(free_image_prepare(H, P, &fi_use, &fi_earns));
-        const double *og = gp, *owl = wlp, *owu = wup;          // the loop's operands
-        double* ow = wp;
-        const int* ofix = a.fixrank;
-        int on = (int)n, onch = H->nchunks, ocfg = rs_cfg;
-        int64_t old = H->ld;                                    // row stride of the image and of the slabs
-        if (fi_use) {
-            const FreeImageBook& b = H->fi;
-            og = c.x; owl = c.xlow; owu = c.xupp; ow = c.s;     // (staging vectors of bh_minor_iterate: free during a bh_pcg)
-            ofix = nullptr;
-            on = (int)b.nfree; onch = (int)(round_up(b.nfree, 16) / 2); ocfg = pick_config(onch);
-            old = b.ldf;                                        // (after a move the live width is smaller than the stride)
-            H->call_bytes = free_image_bytes(H);
-            c.reroute_seq += 1;
-            FreeGatherArgs ga{};
-            ga.g = gp; ga.wl = wlp; ga.wu = wup; ga.fixrank = P->fixrank; ga.map = H->fi_map;
-            ga.gc = c.x; ga.wlc = c.xlow; ga.wuc = c.xupp; ga.wc = c.s; ga.w = wp;
-            ga.n = (int)n; ga.n_pad = (int)n_pad; ga.nfree = on;
-            ga.reroute = c.d_reroute; ga.seq = c.reroute_seq; ga.mirror = a.mirror; ga.tag = a.tag;
-            hipLaunchKernelGGL(free_image_gather_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, s, ga);
-        }
-        const int grid = grid_for(ocfg, nrows);
-        const int nblk = (onch + 15) / 16;
-        double* pbuf[2] = {c.p, c.p2};
-        double* rvbuf[2] = {c.rvpart, c.rvpart + n_pad / 2};
-        const int nch_v = gen_linv ? H->nchunks : (on + 1) / 2;       // proj_apply_linv_kernel also keeps the padding of v at zero
-        const int nrv = fuse_gen ? (nch_v + 63) / 64 : nblk;            // who writes the r.v partials: the projection kernel (64 chunks per workgroup) or the update kernel
-        const int vv_off = (int)(n_pad / 4);                            // v.v partials of the init launch, behind the r.v partials (nrv <= n_pad / 128)
-        if (gen_linv) {
-            if (!P->linv_valid) {
-                hipLaunchKernelGGL(tri_inv_small_kernel, dim3(1), dim3(256), 0, s, (const double*)P->Lr, (int)P->mA, P->W);
-                P->linv_valid = true;
-            }
-            // :705-710 in two launches: tw = A_free mask(g); v = P(g), p_1 = -v and the partials of r.v, v.v.  r = g and w = 0 are
-            // formed by the first update kernel, CgState is set by workgroup 0 of the first H*p launch (init_done = 2).
-            ProjArgs pa = proj_args(P, nullptr, true);
-            hipLaunchKernelGGL(proj_left_mul_kernel, dim3((unsigned)P->mA), dim3(256), 0, s, pa, gp);
-            pa.tpart = P->tw; pa.tpart_nblk = 1; pa.rvpart = rvbuf[0]; pa.vvpart = rvbuf[0] + vv_off; pa.p_out = c.p;
-            pa.W = P->W; pa.nch_pad = H->nchunks; pa.Mgram = linv_refine ? P->M : nullptr; pa.fused_j = 0;
-            hipLaunchKernelGGL((proj_apply_linv_kernel<true>), dim3((unsigned)nrv), dim3(256), 0, s, pa, gp, c.v);
-        } else if (fuse_gen) {
-            // :702-718 by the init kernels: r = g, w = 0, v = P(r), rtv, p_1 = -v (in c.p), tol_cg, CgState (stop_at = 0)
-            hipLaunchKernelGGL((cg_init_kernel<false>), dim3(1), dim3(CG_T), 0, s, a);
-            BH_TRY(launch_project(P, c.r, c.v, c.d_state));
-            hipLaunchKernelGGL(cg_init_finish_kernel, dim3(1), dim3(CG_T), 0, s, a);
-        }
-        int expect_stop_at = H->last_n_hmul > 0 ? H->last_n_hmul + 1 : 0;     // the launch expected to find the loop finished
-        auto launch_stream = [&](int j) -> int32_t {            // H*p of iteration j (1-based), p_j formed on the fly
-            RowStreamArgs ra = rs_args(H, nrows, nullptr);
-            ra.partials = H->partials;
-            if (gram) { ra.J = H->G; ra.d_rows = nrows; ra.mu = 1.0; ra.partials = nullptr; ra.t_out = c.Hp; }     // H*p leaves as one vector
-            if (fi_use) { ra.J = H->Jf; ra.ld = old; ra.nchunks = onch; }
-            if (fuse_gen) { ra.v = c.p; ra.negate = 0; }                            // used by j == 1 only: p_1 = -P(g), formed by the init kernels
-            else { ra.v = og; ra.negate = 1; ra.negmask = ofix; }                  //                      p_1 = -mask(g), formed on the fly
-            CgFuse& f = ra.cf;
-            f.st = c.d_state; f.j = j; f.n = on; f.max_iter = max_iter; f.init_done = gen_linv ? 2 : fuse_gen ? 1 : 0; f.vv_off = vv_off;
-            f.vvec = c.v; f.p_old = pbuf[(j - 1) & 1]; f.p_new = pbuf[j & 1];
-            f.rvpart = rvbuf[(j - 1) & 1]; f.nrv = nrv;
-            f.w = ow; f.wl = owl; f.wu = owu;
-            if (fi_use) { f.reroute = c.d_reroute; f.reroute_seq = c.reroute_seq; }
-            f.sqpart = H->sq_partials; f.gpart = H->sq_partials + H->g_cap;      // one entry per WORKGROUP (up to g_cap of them), not per chunk
-            f.kappa2 = kappa2; f.atol_f2b = atol_f2b;
-            f.trace = a.trace; f.trace_cap = a.trace_cap; f.mirror = a.mirror; f.tag = a.tag;
-            int slot = -1;
-            const bool expect_stop = j == expect_stop_at || j > max_iter || (expect_stop_at == 0 && j > 1);
-            BH_TRY(profile_begin(H, j - 1, &slot));
-            // a handle without history cannot predict its exit: its look-ahead launches (j > 1) take the no-prefetch symbol too, so
-            // that launches which stop in their prologue never show up under the streaming kernel's name in a profile
-            if (gram) launch_gram_cg(rs_cfg, ra, grid, s, expect_stop);
-            else launch_row_stream_cgp(ocfg, ra, grid, s, expect_stop);
-            if (slot >= 0) BH_HIP(hipEventRecord(H->ev[2 * slot + 1], s));
-            return BH_OK;
-        };
-        auto launch_update = [&](int j) -> int32_t {
-            CgUpdArgs u{};
-            u.st = c.d_state; u.j = j; u.partials = H->partials; u.ld = old; u.nchunks = onch; u.G = grid; u.Gs = grid; u.Gq = grid;
-            u.sqpart = H->sq_partials; u.gpart = H->sq_partials + H->g_cap; u.rvpart_in = rvbuf[(j - 1) & 1]; u.rvpart_out = rvbuf[j & 1]; u.nrv = nrv;
-            u.p = pbuf[j & 1]; u.w = ow; u.hw = hw; u.r = c.r; u.g = og; u.v = c.v; u.fixrank = ofix;
-            if (fi_use) { u.map = H->fi_map; u.w_full = wp; u.reroute = c.d_reroute; u.reroute_seq = c.reroute_seq; }
-            u.n = on; u.atol_neg = atol_negcurv; u.trace = a.trace; u.trace_cap = a.trace_cap; u.mirror = a.mirror; u.tag = a.tag;
-            // Gram form: ONE "slab", the finished G p; the partials of dot(p, H*p) and of gamma stay one per workgroup of the G·v grid
-            // (up to n_cu * kMaxBlocksPerCu of them: LaneBatch holds the first 512 in registers and folds the rest in index order)
-            if (gram) { u.partials = c.Hp; u.Gs = 1; }
-            if (!fuse_gen) {
-                if (peer_fused) hipLaunchKernelGGL((cg_reduce_update_kernel<false, true>), dim3(nblk), dim3(256), 0, s, u, g_ctx.peer.args);
-                else hipLaunchKernelGGL((cg_reduce_update_kernel<false, false>), dim3(nblk), dim3(256), 0, s, u, PeerArgs{});
-                return BH_OK;
-            }
-            if (rccl_gen) {
-                hipLaunchKernelGGL(reduce_partials_sq_kernel, dim3(nblk), dim3(256), 0, s, (const double*)H->partials, H->ld, H->nchunks, grid,
-                                   c.hpx, (const double*)H->sq_partials, (int)n_pad, (const CgState*)c.d_state, j);
-                BH_HIP(hipGetLastError());
-                BH_TRY(allreduce_inplace(c.hpx, n_pad + 2, H));
-                u.partials = c.hpx; u.Gs = 1; u.sqpart = c.hpx + n_pad; u.Gq = 1;
-            }
-            // (A, L and the vectors are replicated: past the exchange every rank forms the same partials of A_free r, the same v)
-            u.A = P->Ad; u.ldA = P->ldA; u.mA = (int)P->mA; u.tpart = P->tpart; u.init_in_memory = gen_linv ? 0 : 1;
-            if (peer_fused) hipLaunchKernelGGL((cg_reduce_update_kernel<true, true>), dim3(nblk), dim3(256), 0, s, u, g_ctx.peer.args);
-            else hipLaunchKernelGGL((cg_reduce_update_kernel<true, false>), dim3(nblk), dim3(256), 0, s, u, PeerArgs{});
-            // y = (A_free A_free')^{-1} (A_free r): partial sums + the two triangular solves; then v = r_free - A_free'y and r.v
-            ProjArgs pa = proj_args(P, c.d_state, true);
-            pa.tpart = P->tpart; pa.tpart_nblk = nblk; pa.rvpart = rvbuf[j & 1]; pa.fused_j = j;
-            if (gen_linv) {
-                pa.W = P->W; pa.nch_pad = H->nchunks; pa.Mgram = linv_refine ? P->M : nullptr;
-                hipLaunchKernelGGL((proj_apply_linv_kernel<false>), dim3((unsigned)nrv), dim3(256), 0, s, pa, (const double*)c.r, c.v);
-                return BH_OK;
-            }
-            hipLaunchKernelGGL(trsv_small_kernel, dim3(1), dim3(256), 0, s, pa);
-            hipLaunchKernelGGL((proj_left_mul_tr_kernel<true, 4>), dim3((nch_v + 63) / 64), dim3(256), 0, s, pa, (const double*)c.r, c.v);
-            return BH_OK;
-        };
-        // Launch order: S(1) | U(1) S(2) | U(2) S(3) | ...: the stream kernel of iteration j+1 is what detects "solved" after
-        // iteration j, so it is always enqueued together with U(j) (as a gated no-op if the loop ended in U(j)).
-        BH_TRY(launch_stream(1));
-        int launched = 0;                                          // iterations whose U has been enqueued
-        auto launch_batch = [&](int nb) -> int32_t {
-            nb = std::min(nb, max_iter - launched);
-            for (int i = 0; i < nb; ++i) {
-                BH_TRY(launch_update(launched + 1));
-                BH_TRY(launch_stream(launched + 2));               // (iteration max_iter + 1 only ever runs its prologue: iter > max_iter)
-                launched += 1;
-            }
-            BH_HIP(hipGetLastError());
-            return BH_OK;
-        };
-        const int batch = launch_batch_size(H);
-        MirrorWord mw{};
-        constexpr int kNever = 0x7fffffff;
-        if (rccl_gen) {
-            // every enqueued iteration holds a collective: all ranks must take the same launch decisions, so a decision taken after
-            // S(target + 1) has spoken uses "the loop had ended by iteration `target`" only, never a later state one rank happened
-            // to see (the lock-step schedule of the separate-kernel form, on this form's progress protocol)
-            auto done_by = [&](int target) { return mw.done && mw.n_hmul <= target; };
-            BH_TRY(launch_batch(H->last_n_hmul > 0 ? std::min(H->last_n_hmul, kFirstBatchCap) : 1));
-            BH_TRY(wait_mirror(c, a.tag, kNever, &mw, launched + 1));
-            if (!done_by(launched) && launched < max_iter) {
-                BH_TRY(launch_batch(batch));
-                while (true) {
-                    const int target = launched;
-                    const bool more = launched < max_iter;
-                    if (more) BH_TRY(launch_batch(batch));
-                    BH_TRY(wait_mirror(c, a.tag, kNever, &mw, target + 1));
-                    if (done_by(target) || !more) break;
-                }
-            }
-            BH_TRY(wait_mirror(c, a.tag, kNever, &mw));
-            if (!mw.done) return fail(BH_ERR_HIP, "internal: CG loop did not terminate");
-            fin_out->done = mw.done; fin_out->status = mw.status; fin_out->iter = mw.iter; fin_out->n_hmul = mw.n_hmul;
-            fin_out->tag = a.tag;             // (results_final stays false: over-launched collectives are still in flight)
-            return BH_OK;
-        }
-        const int first = H->last_n_hmul > 0 ? std::min(H->last_n_hmul, kFirstBatchCap) : std::min(batch, 2);
-        BH_TRY(launch_batch(first));
-        // S(launched + 1) speaks for iteration `launched`: either "stopped" (done) or "iter = launched + 1, streaming"
-        BH_TRY(wait_mirror(c, a.tag, kNever, &mw, launched + 1));
-        if (!mw.done && launched < max_iter) {
-            BH_TRY(launch_batch(batch));
-            while (true) {
-                const int target = launched;             // everything enqueued so far except the batch launched next
-                const bool more = launched < max_iter;
-                if (more) BH_TRY(launch_batch(batch));
-                BH_TRY(wait_mirror(c, a.tag, kNever, &mw, target + 1));
-                if (mw.done || !more) break;
-            }
-        }
-        BH_TRY(wait_mirror(c, a.tag, kNever, &mw));          // the final state
-        if (!mw.done) return fail(BH_ERR_HIP, "internal: CG loop did not terminate");
-        if (fi_use && mw.status == kCgReroute) {
-            // a non-finite g on a fixed variable: the full image decides (every compact launch still queued returns at once)
-            H->fi.served -= 1;
-            return pcg_run(H, P, gp, wlp, wup, wp, w_in_ws, kappa2, atol_negcurv, atol_f2b, trace_cap, fin_out, hw, g_pad_zeroed, false);
-        }
-        if (fi_earns) H->fi.credit += free_image_saving(mw.n_hmul, P->nfix, n);
-        fin_out->done = mw.done; fin_out->status = mw.status; fin_out->iter = mw.iter; fin_out->n_hmul = mw.n_hmul;
-        fin_out->results_final = (mw.status == BH_CG_SOLVED || mw.status == BH_CG_MAX_ITER_REACHED || mw.status == BH_CG_NONE);
-        fin_out->tag = a.tag;
-        // exchanges that really ran (one per executed H*p): how many update kernels were ENQUEUED past the exit depends on when
-        // this rank polled its progress word, and those exchange nothing
-        if (peer_fused) H->stats.n_allreduce += mw.n_hmul;
-        return BH_OK;
-    }
-    // Several ranks over RCCL, box constraints: TWO kernels and the collective per iteration.  An ncclAllReduce is
-    // enqueued by the host, so it cannot sit inside the update kernel as the peer-buffer exchange does; instead the update of
-    // iteration j-1 moves into the prologue of the H*p launch of iteration j (row_stream_kernel<..., CGP = 3>: every workgroup
-    // redoes it for the whole 32 KiB vector, the owners of a chunk store it), and the slab reduction packs this rank's share of
-    // p'Hp behind the vector that goes through the all-reduce:  S(1) | R(1) AR(1) S(2) | R(2) AR(2) S(3) | ...
-    // The launch schedule is the lock-step one of the three-kernel form below (decisions on "done by iteration k" only).
-    const bool rccl_fused = !gram && comm_active() && !use_peer_path() && box && g_ctx.opt_cg_fused && rs_cfg >= 0 && cgp3_supported(rs_cfg) &&
-                            max_iter >= 1 && (gp == c.g || n == n_pad);
-    H->stats.cg_kernels = 0;
-    if (rccl_fused) {
-        BH_TRY(hess_ready(H));
-        H->stats.cg_kernels = 2;
-        if (gp == c.g && n < n_pad && !g_pad_zeroed) BH_HIP(hipMemsetAsync(c.g + n, 0, (size_t)(n_pad - n) * sizeof(double), s));
-        const int64_t nrows = H->d + H->q_eff;
-        const int grid = grid_for(rs_cfg, nrows);
-        const int nblk = (H->nchunks + 15) / 16;
-        double* pbuf[2] = {c.p, c.p2};
-        double* rbuf[2] = {c.r, c.r2};
-        double* gbuf[2] = {H->sq_partials + H->g_cap, H->sq_partials + 2 * (int64_t)H->g_cap};       // gamma partials, one per workgroup
-        auto launch_stream = [&](int j) -> int32_t {
-            RowStreamArgs ra = rs_args(H, nrows, nullptr);
-            ra.partials = H->partials;
-            ra.v = gp; ra.negate = 1; ra.negmask = a.fixrank;                // j == 1: p_1 = -mask(g), formed on the fly
-            CgFuse& f = ra.cf;
-            f.st = c.d_state; f.j = j; f.n = (int)n; f.max_iter = max_iter; f.init_done = 0;
-            f.p_old = pbuf[(j - 1) & 1]; f.p_new = pbuf[j & 1];
-            f.r_old = rbuf[(j - 1) & 1]; f.r_new = rbuf[j & 1];
-            f.gpart_in = gbuf[(j - 1) & 1]; f.gpart = gbuf[j & 1];
-            f.w_rw = wp; f.w = wp; f.hw = hw; f.g = gp; f.fixrank = a.fixrank;
-            f.wl = wlp; f.wu = wup;
-            f.sqpart = H->sq_partials;
-            f.Hp = c.hpx; f.sq_index = (int)n_pad;
-            f.kappa2 = kappa2; f.atol_f2b = atol_f2b; f.atol_neg = atol_negcurv;
-            f.trace = a.trace; f.trace_cap = a.trace_cap; f.mirror = a.mirror; f.tag = a.tag;
-            int slot = -1;
-            BH_TRY(profile_begin(H, j - 1, &slot));
-            launch_row_stream_cgp3(rs_cfg, ra, grid, s);
-            if (slot >= 0) BH_HIP(hipEventRecord(H->ev[2 * slot + 1], s));
-            return BH_OK;
-        };
-        auto launch_iteration = [&](int index) -> int32_t {                 // index = j - 1: R(j), AR(j), S(j + 1)
-            const int j = index + 1;
-            hipLaunchKernelGGL(reduce_partials_sq_kernel, dim3(nblk), dim3(256), 0, s, (const double*)H->partials, H->ld, H->nchunks, grid,
-                               c.hpx, (const double*)H->sq_partials, (int)n_pad, (const CgState*)c.d_state, j);
-            BH_HIP(hipGetLastError());
-            BH_TRY(allreduce_inplace(c.hpx, n_pad + 2, H));
-            return launch_stream(j + 1);
-        };
-        BH_TRY(launch_stream(1));
-        const int batch = launch_batch_size(H);
-        int launched = 0;
-        auto launch_batch = [&](int nb) -> int32_t {
-            nb = std::min(nb, max_iter - launched);
-            for (int i = 0; i < nb; ++i) BH_TRY(launch_iteration(launched + i));
-            launched += nb;
-            return BH_OK;
-        };
-        MirrorWord mw{};
-        auto done_by = [&](int target) { return mw.done && mw.n_hmul <= target; };
-        const int first = H->last_n_hmul > 0 ? std::min(H->last_n_hmul, kFirstBatchCap) : 1;
-        BH_TRY(launch_batch(first));
-        BH_TRY(wait_mirror(c, a.tag, launched, &mw));
-        if (!done_by(launched) && launched < max_iter) {
-            BH_TRY(launch_batch(batch));
-            while (true) {
-                const int target = launched;
-                const bool more = launched < max_iter;
-                if (more) BH_TRY(launch_batch(batch));
-                BH_TRY(wait_mirror(c, a.tag, target, &mw));
-                if (done_by(target) || !more) break;
-            }
-        }
-        BH_TRY(wait_mirror(c, a.tag, launched, &mw));
-        if (!mw.done) return fail(BH_ERR_HIP, "internal: CG loop did not terminate");
-        fin_out->done = mw.done; fin_out->status = mw.status; fin_out->iter = mw.iter; fin_out->n_hmul = mw.n_hmul;
-        fin_out->tag = a.tag;
-        return BH_OK;
-    }
-    // Box constraints with register-resident vectors: no init kernel — the first H*p forms p0 = -mask(g) on the fly and
-    // the first step kernel does the initialisation of :702-718 itself.
-    // (g doubles as the H*p input there, so it must be readable up to the padded length: workspace copy or n == ld.)
-    const bool fold_init = box && !multi_panel(H) && ((n + 1) / 2 <= 4 * CG_T) && max_iter >= 1 && g_ctx.opt_fold_init &&
-                           (gp == c.g || n == n_pad);
-    if (fold_init) {
-        if (gp == c.g && n < n_pad && !g_pad_zeroed)   // stale padding of the staged g would be multiplied into the dot products
-            BH_HIP(hipMemsetAsync(c.g + n, 0, (size_t)(n_pad - n) * sizeof(double), s));
-    } else if (box) {
-        hipLaunchKernelGGL((cg_init_kernel<true>), dim3(1), dim3(CG_T), 0, s, a);
-    } else {
-        hipLaunchKernelGGL((cg_init_kernel<false>), dim3(1), dim3(CG_T), 0, s, a);
-        BH_TRY(launch_project(P, c.r, c.v, c.d_state));
-        hipLaunchKernelGGL(cg_init_finish_kernel, dim3(1), dim3(CG_T), 0, s, a);
-    }
-    BH_HIP(hipGetLastError());
+    run.plan = pcg_make_plan(H, P, a.max_iter, gp == c.g || n == n_pad, hw != nullptr, atol_f2b, allow_free_image);
+    const PcgSelection& sel = run.plan.sel;
+    if (sel.shape != PCG_SEPARATE) BH_TRY(hess_ready(H));
+    if (sel.shape == PCG_FUSED && run.plan.gram) BH_TRY(ensure_gram(H));      // G rebuilt first when stale, on the same stream
+    H->stats.cg_kernels = sel.cg_kernels;
+    if (sel.shape != PCG_SEPARATE || sel.fold_init) BH_TRY(zero_staged_g_padding(c, gp, n, n_pad, g_pad_zeroed));
+    bool fi_use = false, fi_earns = false;
+    if (sel.free_image_eligible) BH_TRY(free_image_prepare(H, P, &fi_use, &fi_earns));      // (option free_image)
+    if (fi_use) pcg_use_free_image(run);
 
-    auto launch_iteration = [&](int index) -> int32_t {
-        if (fold_init && index == 0) {
-            // the state still holds the previous call's `done`: this launch is never a no-op, so it is not gated
-            BH_TRY(launch_hmul(H, gp, c.Hp, nullptr, index, true, a.fixrank));                    // :722 with p = -P(g)
-            launch_cg_first_step(a, s);
-            return BH_OK;
-        }
-        BH_TRY(launch_hmul(H, c.p, c.Hp, c.d_state, index));   // :722
-        if (box) {
-            launch_cg_step<0>(a, s);
-        } else {
-            launch_cg_step<1>(a, s);
-            BH_TRY(launch_project(P, c.r, c.v, c.d_state));            // :741
-            launch_cg_step<2>(a, s);
-        }
-        return BH_OK;
-    };
-
-    // Launch schedule.  Kernels of iterations past the exit see state->done and return at once, so over-launching is
-    // cheap (~3 trivial kernels per iteration) but not free.  First a batch sized by the previous call on this handle
-    // (consecutive subproblems of a minor loop behave alike), then, if the loop is still running, launch-ahead batches:
-    // batch k+1 is enqueued before the host looks at batch k's state, so the GPU never waits for the host.
-    const int batch = launch_batch_size(H);
-    int launched = 0;
-    auto launch_batch = [&](int nb) -> int32_t {
-        nb = std::min(nb, max_iter - launched);
-        for (int i = 0; i < nb; ++i) BH_TRY(launch_iteration(launched + i));
-        launched += nb;
-        return BH_OK;
-    };
+    BH_TRY(pcg_launch_first(run));
     // Progress comes back through one host-mapped 8-byte word the kernels store to (no copy kernels, no events).
-    // Multi-rank lock-step: every rank must take the SAME launch decisions (each launched iteration contains an
-    // all-reduce), so a decision taken after waiting for `target` iterations may only use "the loop had exited by
-    // iteration `target`" — never a later state that a slower-polling rank happened to see (the word keeps advancing
-    // while launch-ahead batches run).  done_by(target) is that rank-independent predicate.
     MirrorWord mw{};
-    auto done_by = [&](int target) { return mw.done && mw.n_hmul <= target; };
-    // (an RCCL all-reduce cannot be gated from the device: every over-launched iteration pays for one.  With history on the handle
-    // the first batch is the previous call's count exactly — the prediction the two-kernel form uses for its stop_at launch — so a
-    // repeated subproblem enqueues as many collectives as it has H*p products; without history it stays small.)
-    const bool rccl_path = comm_active() && !use_peer_path();
-    const int first = H->last_n_hmul > 0 ? std::min(H->last_n_hmul, kFirstBatchCap) : std::min(batch, rccl_path ? 1 : 2);
-    BH_TRY(launch_batch(first));
-    BH_TRY(wait_mirror(c, a.tag, launched, &mw));
-    if (!done_by(launched) && launched < max_iter) {
-        BH_TRY(launch_batch(batch));
-        while (true) {
-            const int target = launched;             // everything enqueued so far except the batch launched next
-            const bool more = launched < max_iter;
-            if (more) BH_TRY(launch_batch(batch));
-            BH_TRY(wait_mirror(c, a.tag, target, &mw));
-            if (done_by(target) || !more) break;
-        }
-    }
-    BH_TRY(wait_mirror(c, a.tag, launched, &mw));      // the final state (all enqueued iterations have run or were no-ops)
+    BH_TRY(launch_ahead(run.plan.sched, [&](int index) { return pcg_launch_unit(run, index); },
+                        [&](int n_hmul_target, int iter_target, MirrorWord* m) { return wait_mirror(c, a.tag, n_hmul_target, m, iter_target); }, &mw));
     if (!mw.done) return fail(BH_ERR_HIP, "internal: CG loop did not terminate");
-    fin_out->done = mw.done; fin_out->status = mw.status; fin_out->iter = mw.iter; fin_out->n_hmul = mw.n_hmul;
-    fin_out->tag = a.tag;
+    if (fi_use && mw.status == kCgReroute) {
+        // a non-finite g on a fixed variable: the full image decides (every compact launch still queued returns at once)
+        H->fi.served -= 1;
+        return pcg_run(H, P, gp, wlp, wup, wp, w_in_ws, kappa2, atol_negcurv, atol_f2b, trace_cap, fin_out, hw, g_pad_zeroed, false);
+    }
+    if (fi_earns) H->fi.credit += free_image_saving(mw.n_hmul, P->nfix, n);
+    // (the fused shape with its exchange, if any, inside a kernel; over RCCL over-launched collectives are still in flight)
+    const bool results_final = sel.shape == PCG_FUSED && !sel.rccl_gen &&
+                               (mw.status == BH_CG_SOLVED || mw.status == BH_CG_MAX_ITER_REACHED || mw.status == BH_CG_NONE);
+    pcg_fin_fill(fin_out, mw, a.tag, results_final);
+    // exchanges that really ran (one per executed H*p): how many update kernels were ENQUEUED past the exit depends on when
+    // this rank polled its progress word, and those exchange nothing
+    if (sel.peer_fused) H->stats.n_allreduce += mw.n_hmul;
     return BH_OK;
 }
 
@@ -3443,6 +3423,11 @@ static int32_t adopt_device_mask(bh_proj* P, uint64_t* fix_chunks_out, int* info
 // ------------------------------------------------------------------------------------------
 // cauchy_step: the plan of one search (decided once), its run context, one launcher per form
 // ------------------------------------------------------------------------------------------
+// option cauchy_gram_eq: passes between two formations of a = G D g, B = G D A' from the device-side mask
+// (the smallest power of two at which a formation costs at most 5 % of the passes in between: DESIGN.md §8 f-5)
+constexpr int kCauchyGramEqRefresh = 128;
+constexpr int kDowndateRefresh = 8;     // chol_downdate = 1: breakpoints between two from-scratch factorisations
+
 struct CauchyPlan {
     CauchyForm form = CAUCHY_SWEEP; bool fused = false; int refresh = 0;   // the selection (bh_cauchy_plan.h)
     bool gemm = false;              // row space with equalities: B = J~ D A' by image_b_mfma_kernel (else mA J v sweeps)
@@ -3450,7 +3435,8 @@ struct CauchyPlan {
     bool factor_downdate = false;   // sweeping form: rank-one downdates of the factor itself
     int img_grid = 1, fused_grid = 1, gen_grid = 1, reform_cfg = 0, reform_grid = 1;
     int part_G = 1;                 // how many partial sums a row kernel leaves
-    int off = 0, batch = 1, max_pass = 1;   // the launch-ahead schedule (off: see cauchy_impl)
+    int max_pass = 1;
+    LaunchAhead sched{};            // the launch-ahead schedule (bh_launch_ahead.h)
     bool image() const { return form == CAUCHY_ROWSPACE_BOX || form == CAUCHY_ROWSPACE_EQ; }
     bool reforms_at(int index) const { return refresh > 0 && index > 0 && (index % refresh) == 0; }
 };
@@ -3502,8 +3488,11 @@ static CauchyPlan cauchy_make_plan(const bh_hess* H, const bh_proj* P) {
     p.part_G = (p.form == CAUCHY_ROWSPACE_EQ && p.gen_tiled) ? p.gen_grid : p.img_grid;
     p.max_pass = (int)(H->n + 1);
     // image-space passes take ~17 us: keep a deeper queue ahead of the GPU (over RCCL every over-launched pass costs a collective)
-    p.batch = (!p.image() && p.form != CAUCHY_GRAM_EQ) ? launch_batch_size(H) : (comm_active() && !use_peer_path()) ? 4 : 8;
-    p.off = p.fused ? 1 : 0;
+    p.sched.batch = (!p.image() && p.form != CAUCHY_GRAM_EQ) ? launch_batch_size(H) : (comm_active() && !use_peer_path()) ? 4 : 8;
+    // (fused form: launch k carries decision k-1, so u launches stand for u - 1 passes)
+    p.sched.off = p.fused ? 1 : 0;
+    p.sched.max_units = p.max_pass + p.sched.off; p.sched.first = 2 + p.sched.off;
+    p.sched.await_iter = false; p.sched.lock_step = true; p.sched.look_first = false;
     return p;
 }
 
@@ -3805,9 +3794,7 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     a.fixrank = P->fixrank; a.n = (int)n; a.n_pad = (int)H->ld; a.nmm = (int)(n - mA);
     a.delta = delta; a.atol = std::sqrt(2.220446049250313e-16);
     a.box = (mA == 0) ? 1 : 0;
-    c.tag = (c.tag + 1) & 0xffffu;
-    if (c.tag == 0) c.tag = 1;
-    a.mirror = c.d_mirror; a.tag = c.tag;
+    a.mirror = c.d_mirror; a.tag = next_mirror_tag(c);
 
     run.plan = cauchy_make_plan(H, P);
     const CauchyPlan& plan = run.plan;
@@ -3818,11 +3805,9 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     P->mask_epoch = ++g_mask_epoch;
     hipLaunchKernelGGL(cauchy_init_kernel, dim3(1), dim3(CG_T), 0, s, a);
     if (mA > 0) BH_TRY(launch_reduced_factor(P, true, nullptr));
-    const int max_pass = plan.max_pass;
-    int launched = 0;
     MirrorWord mw{};
-    const bool gram_search = plan.form == CAUCHY_GRAM;
-    if (gram_search) {
+    if (plan.form == CAUCHY_GRAM) {
+        const int launched = plan.max_pass, off = plan.sched.off;   // one launch stands for every pass; off = 0 (not the one-kernel row-space form)
         BH_TRY(launch_hmul(H, c.p, c.Hp, c.d_state, -1));           // Hd = H*d    :609  (rebuilds G first when it is stale)
         H->stats.n_hmul += 1;
         CauchyGramArgs ga{};
@@ -3830,30 +3815,13 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
         if (n <= 8 * CA_T) hipLaunchKernelGGL(cauchy_gram_kernel<true>, dim3(1), dim3(CA_T), 0, s, ga);
         else hipLaunchKernelGGL(cauchy_gram_kernel<false>, dim3(1), dim3(CA_T), 0, s, ga);
         BH_HIP(hipGetLastError());
-        launched = max_pass;                                        // the kernel publishes once, when its loop has ended
+        BH_TRY(wait_mirror(c, a.tag, launched - off, &mw));        // the kernel publishes once, when its loop has ended
+    } else {
+        // The launch-ahead schedule of bh_launch_ahead.h, lock-step (mirror: status field = error flag, iter field = breakpoints,
+        // n_hmul = passes run).
+        BH_TRY(launch_ahead(plan.sched, [&](int index) { return cauchy_launch_pass(run, index); },
+                            [&](int n_hmul_target, int iter_target, MirrorWord* m) { return wait_mirror(c, a.tag, n_hmul_target, m, iter_target); }, &mw));
     }
-    const int batch = plan.batch;
-    // (fused form: launch k carries decision k-1, so `launched` launches stand for launched - 1 passes)
-    const int off = plan.off;
-    const int max_launch = max_pass + off;
-    auto launch_batch = [&](int nb) -> int32_t {
-        nb = std::min(nb, max_launch - launched);
-        for (int i = 0; i < nb; ++i) BH_TRY(cauchy_launch_pass(run, launched + i));
-        launched += nb;
-        return BH_OK;
-    };
-    // Same launch-ahead schedule and the same rank-independent exit predicate as pcg_run (mirror: status field = error
-    // flag, iter field = breakpoints, n_hmul = passes run).
-    auto done_by = [&](int target) { return mw.done && mw.n_hmul <= target; };
-    if (!gram_search) BH_TRY(launch_batch(2 + off));
-    while (!gram_search) {
-        const int target = launched - off;
-        const bool more = launched < max_launch;
-        if (more) BH_TRY(launch_batch(batch));
-        BH_TRY(wait_mirror(c, a.tag, target, &mw));
-        if (done_by(target) || !more) break;
-    }
-    BH_TRY(wait_mirror(c, a.tag, launched - off, &mw));
     // (fused form: decision j is taken by launch j+1, which writes s_c into buffer (j+1) & 1)
     BH_TRY(fetch_vec(s_out, plan.fused ? run.sbuf[mw.n_hmul & 1] : c.w, n, dev));
     int info_host = 0;
