@@ -51,6 +51,7 @@ struct CgWorkspace {
     double *w = nullptr, *r = nullptr, *v = nullptr, *p = nullptr, *Hp = nullptr, *g = nullptr, *wl = nullptr, *wu = nullptr;
     double *x = nullptr, *s = nullptr, *xlow = nullptr, *xupp = nullptr;   // minor_iterate staging
     double* hw = nullptr;          // H*w accumulated by the CG loop for minor_iterate's linesearch
+    double* hwc = nullptr;         // ... its free part in slot order, when that loop ran on the compact image (option free_image_minor)
     double *p2 = nullptr, *gpart = nullptr, *rvpart = nullptr;   // two-kernel box iteration: p ping-pong, (spare), r.v partials (2 x n_pad/2)
     double *r2 = nullptr, *hpx = nullptr, *hpx_tail = nullptr;   // RCCL form of it: r ping-pong; H*p with the p'Hp slot right behind it (hpx[n_pad] = hpx_tail[0])
     double* slab = nullptr;
@@ -157,6 +158,9 @@ struct Ctx {
     int64_t opt_proj_form = 1;       // 1: reduced mA x mA form (fast), 0: the reference's augmented mpp x mpp form
     int64_t opt_upload_chunk_mb = 64; // bh_hess_create_async: MiB of J per pipelined column chunk
     int64_t opt_free_image = 1;      // box CG loop, one rank: stream the compact image of the free columns (0 off, 1 by the policy of bh_free_image_plan.h, 2 always)
+    // bh_minor_iterate* with ls_from_cg = 1 and step_from_cg = 0: the call is considered for the compact image like a bh_pcg* (the
+    // loop accumulates the free part of H*w, free_image_linesearch_kernel takes the line search on the compact operands); 0: never
+    int64_t opt_free_image_minor = 0;
     int64_t opt_gram_ingest = 0;     // bh_hess_create_async, one rank, n <= 16384: the handle is born in the Gram form, G built during the upload
     int64_t opt_ev_stride = 8;       // BH_FLAG_PROFILE: hipEvents around every opt_ev_stride-th H*p launch of a handle
     // RCCL
@@ -507,12 +511,12 @@ int32_t ensure_cg_workspace(int64_t n_pad, int64_t trace_cap) {
     CgWorkspace& c = g_ctx.cg;
     if (c.n_pad < n_pad) {
         // order matters: the host-pointer entry points stage (g, wl, wu), (s, x, xlow, xupp, g) or (x, xlow, xupp, g) with ONE DMA
-        double** vecs[] = {&c.w, &c.r, &c.v, &c.p, &c.Hp, &c.s, &c.x, &c.xlow, &c.xupp, &c.g, &c.wl, &c.wu, &c.hw, &c.p2, &c.gpart, &c.rvpart,
+        double** vecs[] = {&c.w, &c.r, &c.v, &c.p, &c.Hp, &c.s, &c.x, &c.xlow, &c.xupp, &c.g, &c.wl, &c.wu, &c.hw, &c.hwc, &c.p2, &c.gpart, &c.rvpart,
                            &c.r2, &c.hpx, &c.hpx_tail};
-        constexpr int NV = 19;
+        constexpr int NV = 20;
         dev_free(c.slab);
         c.slab = nullptr;
-        g_ctx.hw_note = {};                      // cg.hw goes with the old slab
+        g_ctx.hw_note = {};                      // cg.hw and cg.hwc go with the old slab
         BH_TRY(dev_alloc(&c.slab, NV * n_pad + 8));
         BH_HIP(hipMemsetAsync(c.slab, 0, (size_t)(NV * n_pad + 8) * sizeof(double), g_ctx.stream));
         for (int i = 0; i < NV; ++i) *vecs[i] = c.slab + (int64_t)i * n_pad;
@@ -1568,6 +1572,11 @@ int32_t bh_set_option(const char* key, int64_t value) {
         g_ctx.opt_free_image = value;
         return BH_OK;
     }
+    if (!strcmp(key, "free_image_minor")) {
+        if (value != 0 && value != 1) return fail(BH_ERR_INVALID_ARG, "free_image_minor is 0 or 1");
+        g_ctx.opt_free_image_minor = value;
+        return BH_OK;
+    }
     if (!strcmp(key, "gram_ingest")) {
         if (value != 0 && value != 1) return fail(BH_ERR_INVALID_ARG, "gram_ingest is 0 or 1");
         g_ctx.opt_gram_ingest = value;
@@ -2413,7 +2422,8 @@ int32_t bh_left_mul_tr(bh_proj* P, const double* y, double* out_n) {
 // results_final: every kernel that writes w (or H*w) had COMPLETED before the launch that published `done` started (two-kernel
 // iteration, loop stopped by the exit test in an H*p launch's prologue: solved / iterations exhausted).  The device-pointer entry
 // point then returns without draining the stream: what is still in flight are prologue-only launches that write nothing.
-struct PcgFin { int done, status, iter, n_hmul; bool results_final = false; unsigned tag = 0; };
+// compact: the loop ran on the compact image of the free columns and left compact operands (a call handed back reports false).
+struct PcgFin { int done, status, iter, n_hmul; bool results_final = false; unsigned tag = 0; bool compact = false; };
 
 static void pcg_fin_fill(PcgFin* fin, const MirrorWord& mw, unsigned tag, bool results_final) {
     fin->done = mw.done; fin->status = mw.status; fin->iter = mw.iter; fin->n_hmul = mw.n_hmul;
@@ -2584,8 +2594,8 @@ static void pcg_fused_geometry(PcgPlan& p, const bh_hess* H, int nch, int n_loop
 }
 
 // Decides everything about the call from the handles and the options.  Launches and allocates nothing.
-static PcgPlan pcg_make_plan(const bh_hess* H, const bh_proj* P, int max_iter, bool g_padded, bool hw_wanted, double atol_f2b,
-                             bool allow_free_image) {
+static PcgPlan pcg_make_plan(const bh_hess* H, const bh_proj* P, int max_iter, bool g_padded, bool hw_wanted, bool hw_free_part_ok,
+                             double atol_f2b, bool allow_free_image) {
     const CgWorkspace& c = g_ctx.cg;
     const int64_t n = H->n, n_pad = H->ld;
     PcgPlan p;
@@ -2599,7 +2609,7 @@ static PcgPlan pcg_make_plan(const bh_hess* H, const bh_proj* P, int max_iter, b
     in.reduced = P->reduced; in.tpart = P->tpart != nullptr; in.W = P->W != nullptr; in.M_valid = P->M_valid; in.lda_is_ld = P->ldA == H->ld;
     in.rs_cfg_ok = rs_cfg >= 0; in.cgp3_ok = rs_cfg >= 0 && cgp3_supported(rs_cfg); in.peer_blocks_fit = (H->nchunks + 15) / 16 <= kPeerBlkCap;
     in.iterates = max_iter >= 1; in.g_padded = g_padded; in.vectors_in_regs = (n + 1) / 2 <= 4 * CG_T;
-    in.hw_wanted = hw_wanted; in.atol_f2b_positive = atol_f2b > 0; in.allow_free_image = allow_free_image;
+    in.hw_wanted = hw_wanted; in.hw_free_part_ok = hw_wanted && hw_free_part_ok; in.atol_f2b_positive = atol_f2b > 0; in.allow_free_image = allow_free_image;
     p.sel = pcg_select(in);
     const int batch = launch_batch_size(H);
     const bool rccl_path = comm_active() && !use_peer_path();
@@ -2631,13 +2641,15 @@ static PcgPlan pcg_make_plan(const bh_hess* H, const bh_proj* P, int max_iter, b
 }
 
 // The loop moves to the compact image of the free columns: compact operands (staging vectors of bh_minor_iterate: free during a
-// bh_pcg), no mask, the geometry of the compact width.
+// bh_pcg, and read for the last time by step_bounds_kernel in front of a bh_minor_iterate's loop), no mask, the geometry of the
+// compact width.  A wanted H*w is accumulated in slot order, its free part only (bh_pcg_plan.h: hw_free_part_ok).
 static void pcg_use_free_image(PcgRun& r) {
     bh_hess* H = r.H; CgWorkspace& c = r.c;
     const FreeImageBook& b = H->fi;
     r.fi_use = true;
     r.og = c.x; r.owl = c.xlow; r.owu = c.xupp; r.ow = c.s;
     r.ofix = nullptr;
+    if (r.hw != nullptr) r.hw = c.hwc;
     r.on = (int)b.nfree; r.onch = (int)(round_up(b.nfree, 16) / 2);
     r.old = b.ldf;                                            // (after a move the live width is smaller than the stride)
     pcg_fused_geometry(r.plan, H, r.onch, r.on);
@@ -2855,7 +2867,8 @@ static int32_t pcg_launch_unit(PcgRun& r, int index) {
 static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* wlp, const double* wup, double* wp, bool w_in_ws,
                        double kappa2, double atol_negcurv, double atol_f2b, int64_t trace_cap, PcgFin* fin_out, double* hw = nullptr,
                        bool g_pad_zeroed = false /* the staged copy of g arrived with its padding already zero */,
-                       bool allow_free_image = true /* false: the compact loop handed this call back (bh_freeimg.hip.h) */) {
+                       bool allow_free_image = true /* false: the compact loop handed this call back (bh_freeimg.hip.h) */,
+                       bool hw_free_part_ok = false /* nothing reads hw on the fixed variables (option free_image_minor) */) {
     const int64_t n = H->n, n_pad = H->ld;
     const int64_t max_iter64 = 2 * (n - P->mA - P->nfix);   // src/basic_tralcnlss.jl:714
     if (max_iter64 < 0) return fail(BH_ERR_PRECONDITION, "n - mA - count(fixvars) < 0");
@@ -2878,7 +2891,7 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
     run.on = (int)n; run.onch = H->nchunks; run.old = H->ld;
     run.expect_stop_at = H->last_n_hmul > 0 ? H->last_n_hmul + 1 : 0;
 
-    run.plan = pcg_make_plan(H, P, a.max_iter, gp == c.g || n == n_pad, hw != nullptr, atol_f2b, allow_free_image);
+    run.plan = pcg_make_plan(H, P, a.max_iter, gp == c.g || n == n_pad, hw != nullptr, hw_free_part_ok, atol_f2b, allow_free_image);
     const PcgSelection& sel = run.plan.sel;
     if (sel.shape != PCG_SEPARATE) BH_TRY(hess_ready(H));
     if (sel.shape == PCG_FUSED && run.plan.gram) BH_TRY(ensure_gram(H));      // G rebuilt first when stale, on the same stream
@@ -2904,6 +2917,7 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
     const bool results_final = sel.shape == PCG_FUSED && !sel.rccl_gen &&
                                (mw.status == BH_CG_SOLVED || mw.status == BH_CG_MAX_ITER_REACHED || mw.status == BH_CG_NONE);
     pcg_fin_fill(fin_out, mw, a.tag, results_final);
+    fin_out->compact = fi_use;
     // exchanges that really ran (one per executed H*p): how many update kernels were ENQUEUED past the exit depends on when
     // this rank polled its progress word, and those exchange nothing
     if (sel.peer_fused) H->stats.n_allreduce += mw.n_hmul;
@@ -3134,11 +3148,21 @@ static int32_t minor_iterate_impl(bh_hess* H, bh_proj* P, const double* x, const
     hipLaunchKernelGGL(step_bounds_kernel, dim3(grid), dim3(256), 0, g_ctx.stream, xp, sp, lop, upp,
                        P->nfix > 0 ? P->fixrank : (const int*)nullptr, delta, (int)n, c.wl, c.wu);
     PcgFin fin{};
-    BH_TRY(pcg_run(H, P, gp, c.wl, c.wu, wp, wp == c.w, kappa2, atol_negcurv, atol_f2b, 0, &fin, hw, !dev));
+    // free_image_minor: with step_from_cg off the line search's w'Hw is the only consumer of hw, and w is zero on the fixed
+    // variables — the free part of H*w is enough, so the loop may run on the compact image
+    const bool hw_free_part_ok = hw != nullptr && g_ctx.opt_free_image_minor == 1 && g_ctx.opt_step_from_cg == 0;
+    BH_TRY(pcg_run(H, P, gp, c.wl, c.wu, wp, wp == c.w, kappa2, atol_negcurv, atol_f2b, 0, &fin, hw, !dev, true, hw_free_part_ok));
     double alpha = std::nan("");
     const bool do_ls = fin.status != BH_CG_NEGATIVE_CURVATURE;       // :669
     // alpha is written by the line search straight into the host-mapped mailbox (no DMA of its own)
-    if (do_ls) BH_TRY(launch_linesearch(H, P, gp, wp, c.wl, c.wu, true, hw, mbox_dev<double>(kMbScal)));
+    if (do_ls && fin.compact && hw_free_part_ok) {
+        // the compact operands the loop left (pcg_use_free_image): g, w, w_l, w_u in slot order and the free part of H*w
+        hipLaunchKernelGGL(free_image_linesearch_kernel, dim3(1), dim3(CG_T), 0, g_ctx.stream, (const double*)c.x, c.s, (const double*)c.xlow,
+                           (const double*)c.xupp, (const double*)c.hwc, (const int*)H->fi_map, wp, (int)H->fi.nfree, mbox_dev<double>(kMbScal));
+        BH_HIP(hipGetLastError());
+    } else if (do_ls) {
+        BH_TRY(launch_linesearch(H, P, gp, wp, c.wl, c.wu, true, hw, mbox_dev<double>(kMbScal)));
+    }
     if (wp == c.w) BH_TRY(fetch_vec(w_out, c.w, n, dev));
     if (!dev) {
         BH_TRY(sync_flush());                               // w comes back through the pinned arena: the stream is drained
@@ -3150,8 +3174,9 @@ static int32_t minor_iterate_impl(bh_hess* H, bh_proj* P, const double* x, const
         BH_TRY(finish_device_call());
     }
     BH_TRY(pcg_finish(H, fin, !dev));
-    // cg.hw now holds H*w for the w just delivered (scaled with it by the line search): bh_step_accumulate_dev may use it
-    if (dev && hw != nullptr) { g_ctx.hw_note.H = H; g_ctx.hw_note.w = w_out; g_ctx.hw_note.gm = g_model; }
+    // cg.hw now holds H*w for the w just delivered (scaled with it by the line search): bh_step_accumulate_dev may use it.
+    // Not after a loop on the compact image: that one left the free part of H*w in cg.hwc and cg.hw as it was.
+    if (dev && hw != nullptr && !fin.compact) { g_ctx.hw_note.H = H; g_ctx.hw_note.w = w_out; g_ctx.hw_note.gm = g_model; }
     if (status) *status = fin.status;
     if (iters) *iters = fin.iter;
     if (n_hmul_out) *n_hmul_out = fin.n_hmul;

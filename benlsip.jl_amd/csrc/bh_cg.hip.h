@@ -537,13 +537,14 @@ __global__ __launch_bounds__(256) void step_bounds_kernel(const double* __restri
     }
 }
 
-// linesearch — src/basic_tralcnlss.jl:766-791, given wHw = vthv(H,w) in wHw[0]; optionally scales w by alpha in place
-// (minor_iterate :670-671).  out[0] = alpha.  Single workgroup.
-__global__ __launch_bounds__(CG_T) void linesearch_kernel(const double* __restrict__ g, double* __restrict__ w,
-                                                          const double* __restrict__ wl, const double* __restrict__ wu,
-                                                          const int* __restrict__ fixrank, const double* __restrict__ wHw_p,
-                                                          double* __restrict__ hw, int n, int scale_w, double* __restrict__ out) {
-    __shared__ double scratch[2 * (CG_T / 64)];
+// The step length of linesearch — src/basic_tralcnlss.jl:766-791 — over the n entries the vectors hold, by one workgroup of CG_T
+// threads: entry i belongs to thread i mod CG_T, in ascending order.  Shared by linesearch_kernel (the full vectors, the mask
+// from fixrank) and free_image_linesearch_kernel (bh_freeimg.hip.h: the compact vectors, fixrank = NULL, every entry free).
+// hw != NULL: w'Hw = w.hw, else it is taken from wHw_p[0].  Every thread returns the same alpha; the last barrier of the
+// reductions stands between the reads of w here and whatever the caller stores afterwards.
+__device__ __forceinline__ double linesearch_alpha(const double* __restrict__ g, const double* __restrict__ w, const double* __restrict__ wl,
+                                                   const double* __restrict__ wu, const int* __restrict__ fixrank,
+                                                   const double* __restrict__ wHw_p, const double* __restrict__ hw, int n, double* scratch) {
     const double INF = __longlong_as_double(0x7ff0000000000000ll);
     OpMinNan opmin;
     double gw[1] = {0.0}, amin[1] = {INF}, whw[1] = {0.0};
@@ -561,7 +562,17 @@ __global__ __launch_bounds__(CG_T) void linesearch_kernel(const double* __restri
     if (hw != nullptr) block_reduce<CG_T, 1>(whw, scratch, OpSum(), 0.0);
     const double wHw = (hw != nullptr) ? whw[0] : wHw_p[0];
     const double alpha_opt = (wHw > 0.0) ? __ddiv_rn(-gw[0], wHw) : INF;      // :776
-    const double alpha = opmin(alpha_opt, amin[0]);                            // :790
+    return opmin(alpha_opt, amin[0]);                                          // :790
+}
+
+// linesearch — src/basic_tralcnlss.jl:766-791, given wHw = vthv(H,w) in wHw[0]; optionally scales w by alpha in place
+// (minor_iterate :670-671).  out[0] = alpha.  Single workgroup.
+__global__ __launch_bounds__(CG_T) void linesearch_kernel(const double* __restrict__ g, double* __restrict__ w,
+                                                          const double* __restrict__ wl, const double* __restrict__ wu,
+                                                          const int* __restrict__ fixrank, const double* __restrict__ wHw_p,
+                                                          double* __restrict__ hw, int n, int scale_w, double* __restrict__ out) {
+    __shared__ double scratch[2 * (CG_T / 64)];
+    const double alpha = linesearch_alpha(g, w, wl, wu, fixrank, wHw_p, hw, n, scratch);
     if (scale_w)
         for (int i = threadIdx.x; i < n; i += CG_T) {
             w[i] = __dmul_rn(alpha, w[i]);   // :671

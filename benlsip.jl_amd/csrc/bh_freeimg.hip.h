@@ -1,5 +1,5 @@
-// bh_freeimg.hip.h — the compact image of the free columns (option "free_image"): build, column moves, and the gather in front
-// of the box-constrained CG loop that runs on it
+// bh_freeimg.hip.h — the compact image of the free columns (option "free_image"): build, column moves, the gather in front
+// of the box-constrained CG loop that runs on it, and the line search behind it (option "free_image_minor")
 // Part of the single translation unit of bh_api.hip (see bh_kernels.hip.h for the layout and design notes).
 //
 // In the box-constrained CG loop every p_j is zero on the fixed variables, and their entries of H*p are used for nothing
@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bh_reduce.hip.h"
+#include "bh_cg.hip.h"
 
 namespace bh {
 
@@ -99,6 +100,29 @@ __global__ __launch_bounds__(256) void free_image_gather_kernel(FreeGatherArgs a
             }
         }
     }
+}
+
+// minor_iterate's line search and scaling (src/basic_tralcnlss.jl:669-672) behind a CG loop that ran on the compact image (option
+// "free_image_minor"): the operands are the compact vectors the loop left — g, w_l, w_u as the gather wrote them, w, and hw, the
+// FREE part of H*w accumulated by cg_reduce_update_kernel.  w is zero on the fixed variables, so g.w and w.Hw over the nfree
+// slots are the sums of linesearch_kernel without its zero terms, and no mask is needed: every live slot is free.  Slot i belongs
+// to thread i mod CG_T in both passes, as in linesearch_kernel on n = nfree (linesearch_alpha is the shared arithmetic).
+// The scaled w goes into the compact buffer and, from the same thread, into the caller's w at map[i]; alpha into out[0].
+// The caller's w keeps the +0 the gather wrote on the fixed variables: with a negative or non-finite alpha linesearch_kernel would
+// leave alpha * 0 there (-0 or NaN).  hw is not scaled: nothing reads it after this launch.
+__global__ __launch_bounds__(CG_T) void free_image_linesearch_kernel(const double* __restrict__ gc, double* __restrict__ wc,
+                                                                     const double* __restrict__ wlc, const double* __restrict__ wuc,
+                                                                     const double* __restrict__ hwc, const int* __restrict__ map,
+                                                                     double* __restrict__ w_full, int nfree, double* __restrict__ out) {
+    __shared__ double scratch[2 * (CG_T / 64)];
+    const double alpha = linesearch_alpha(gc, wc, wlc, wuc, nullptr, nullptr, hwc, nfree, scratch);
+    for (int i = threadIdx.x; i < nfree; i += CG_T) {
+        const double wi = __dmul_rn(alpha, wc[i]);          // :671
+        wc[i] = wi;
+        const int m = map[i];                                // (i < nfree: a column of the caller's w)
+        if (m >= 0) w_full[m] = wi;
+    }
+    if (threadIdx.x == 0) out[0] = alpha;
 }
 
 }  // namespace bh

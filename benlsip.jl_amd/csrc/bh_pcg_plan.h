@@ -29,6 +29,8 @@ struct PcgSelectIn {
     bool hw_wanted;               // the caller wants H*w accumulated (bh_minor_iterate)
     bool atol_f2b_positive;
     bool allow_free_image;        // false: the compact loop handed this call back
+    bool hw_free_part_ok;         // the free part of the accumulated H*w is enough: hw is wanted, option free_image_minor is on and
+                                  // step_from_cg is off (the only consumer left is the line search's w'Hw, and w is zero where fixed)
 };
 
 struct PcgSelection {
@@ -74,8 +76,10 @@ inline PcgSelection pcg_select(const PcgSelectIn& in) {
         // (one equality: the "factor" is a scalar, y = t / l^2 has no conditioning to repair)
         o.linv_refine = gen_linv && in.linv_refine != 0 && in.M_valid && in.mA >= 2;
         o.cg_kernels = (box ? 2 : gen_linv ? 3 : 4) + (rccl_gen ? 1 : 0);
-        // Box constraints, one rank, implicit form, no H*w wanted: the loop may run on the compact image of the free columns
-        o.free_image_eligible = in.allow_free_image && box && !in.gram_handle && !in.comm && !in.hw_wanted && in.atol_f2b_positive;
+        // Box constraints, one rank, implicit form, no H*w wanted or only its free part: the loop may run on the compact image of
+        // the free columns
+        o.free_image_eligible = in.allow_free_image && box && !in.gram_handle && !in.comm && (!in.hw_wanted || in.hw_free_part_ok) &&
+                                in.atol_f2b_positive;
         return o;
     }
     // Several ranks over RCCL, box constraints: TWO kernels and the collective per iteration — the update of iteration j-1 moves

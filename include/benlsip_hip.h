@@ -198,7 +198,8 @@ int32_t bh_hess_shape(const bh_hess* H, int64_t* d, int64_t* n, int64_t* q);
  * bh_hess_free_image_info: state = 0 none, 1 valid, 2 stale — with `lincons` given: an image exists but describes another
  * active set than the current one of `lincons` (newly fixed variables are moved out by the next eligible call when that pays;
  * a freed variable needs a rebuild); with NULL an existing image reports 1.  width = its live columns (0: none), builds and
- * moves (columns) = since the handle was created, calls_served = bh_pcg* calls whose CG loop ran on it.  Any pointer may be NULL.
+ * moves (columns) = since the handle was created, calls_served = bh_pcg* (and, under option "free_image_minor", bh_minor_iterate*)
+ * calls whose CG loop ran on it.  Any pointer may be NULL.
  * bh_hess_free_image_read (debugging and tests): the image as it lies in memory, rows x stride doubles row-major (columns from
  * width on are zero), and the slot -> original column map (stride ints, -1 from width on).  rows / stride are always reported;
  * a NULL buffer is skipped; BH_ERR_PRECONDITION when the handle has no image, BH_ERR_INVALID_ARG when a buffer is too small. */
@@ -471,9 +472,22 @@ int32_t bh_stats_reset(bh_hess* H);
  *                        leaves the handle on the full image without an error.  status, iters, n_hmul, the trace and the tie log keep
  *                        their meaning; w is exactly 0 on the fixed variables; p'Hp and r.v are summed in the order of the compact
  *                        columns (another rounding than on the full image).  A non-finite g on a fixed variable: the call runs on the
- *                        full image.  bh_minor_iterate* (it wants H*w), linear equalities, several ranks and the Gram form are never
- *                        eligible.  bh_hess_free_image_info reports what the handle holds.  Another value: BH_ERR_INVALID_ARG.
+ *                        full image.  Linear equalities, several ranks and the Gram form are never eligible; bh_minor_iterate* with
+ *                        "ls_from_cg" = 1 (it wants H*w) is eligible only under "free_image_minor".  bh_hess_free_image_info reports
+ *                        what the handle holds.  Another value: BH_ERR_INVALID_ARG.
  *                        (The environment variable BH_FREE_IMAGE, read by bh_init, sets the initial value.)
+ *   "free_image_minor" [0] 1 = a bh_minor_iterate* call with "ls_from_cg" = 1 is considered for the compact image by the rules and the
+ *                        policy of "free_image" (0 off, 1 by the policy, 2 always), provided "step_from_cg" = 0 at the time of the call:
+ *                        the line search's w'Hw is then the only reader of the accumulated H*w, and w is zero on the fixed variables,
+ *                        so the CG loop accumulates the FREE part of H*w in slot order and the line search (free_image_linesearch_kernel)
+ *                        runs on the compact operands, delivering the scaled w through the slot -> column map.  g.w and w'Hw are summed in
+ *                        the order of the compact columns.  w stays +0 on the fixed variables whatever alpha is (on the full image a
+ *                        negative or non-finite alpha leaves alpha * 0 = -0 or NaN there).  After such a call bh_step_accumulate_dev
+ *                        always recomputes H*s + g (the fixed part of H*w was never formed), also when "step_from_cg" is switched on
+ *                        in between.  A call handed back to the full image (non-finite g on a fixed variable) is today's in every bit.
+ *                        With "step_from_cg" = 1 (the resident inner-step chain) the call stays on the full image.  calls_served of
+ *                        bh_hess_free_image_info counts these calls too.  0 = bh_minor_iterate* with "ls_from_cg" = 1 never touches the
+ *                        image.  Another value: BH_ERR_INVALID_ARG.
  *   "gram_ingest"    [0] bh_hess_create_async on one rank with n <= 16384: 1 = the handle is born in the Gram form and G is built during
  *                        the upload, block rows of G as their columns land (see bh_hess_create_async).  Several ranks or n > 16384: the
  *                        call is what it is with 0 (an implicit handle).  Read when the handle is created; no effect on
