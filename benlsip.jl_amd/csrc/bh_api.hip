@@ -135,6 +135,7 @@ struct Ctx {
     int64_t opt_cauchy_image_max_ma = 64;   // ... and with up to this many linear equalities (0..64)
     int64_t opt_cauchy_image_refresh = 0;   // row-space search, one rank: R >= 1 forms t_d, t_s (a, B, t_s) again from J every R-th pass (0: never)
     int64_t opt_cauchy_fused = 1;           // box constraints, one rank, row-space form: ONE kernel per breakpoint (cauchy_fused_kernel)
+    int64_t opt_cauchy_block = 0;           // ... and K = 2, 4, 8 or 16 breakpoints per launch of it (cauchy_block_kernel<K>; 0, 1: one)
     int64_t opt_cauchy_gram_eq = 0;         // Gram-form handle, 1 <= mA <= 64, one rank: the search with linear equalities from G (cauchy_gram_eq_kernel)
     int64_t opt_cauchy_gram = 0;            // Gram-form handle, box constraints, one rank: the whole search from G in one launch (cauchy_gram_kernel)
     int64_t opt_linv_refine = 1;            // explicit-inverse projection (three-kernel CG iteration): one step of iterative refinement of y
@@ -434,6 +435,7 @@ struct bh_hess {
     double* timg = nullptr;        // 2 x (d + q) + 2 x kCauchyImgGrid: t_d = J~ d, t_s = J~ s_c and the partial sums of the image-space Cauchy search (lazy)
     double* timg_gen = nullptr;    // (1 + mA) x (d + q): a = J~ D g and B = J~ D A' of its linear-equality form (lazy, grown on demand)
     int64_t timg_gen_doubles = 0;
+    double* cblk = nullptr;        // option cauchy_block: third s_c buffer (ld), two CauchyBlockRec, 2 x [16][2][kCauchyFusedGrid] partial sums (lazy)
     double* partials = nullptr;    // g_cap x ld
     double* sq_partials = nullptr; // 2 x g_cap (second half: per-workgroup minima of the two-kernel CG iteration)
     double* scalar = nullptr;      // 2
@@ -1464,6 +1466,7 @@ int32_t bh_init(int32_t device, int32_t flags) {
     if (const char* s = getenv("BH_CG_FUSED")) g_ctx.opt_cg_fused = std::min<int64_t>(std::max<int64_t>(0, atoll(s)), 2);
     if (const char* s = getenv("BH_FINAL_SYNC")) g_ctx.opt_final_sync = atoll(s) ? 1 : 0;
     if (const char* s = getenv("BH_FREE_IMAGE")) g_ctx.opt_free_image = std::min<int64_t>(std::max<int64_t>(0, atoll(s)), 2);
+    if (const char* s = getenv("BH_CAUCHY_BLOCK")) { if (cauchy_block_value_ok(atoll(s))) g_ctx.opt_cauchy_block = atoll(s); }
     g_ctx.init = true;
     return BH_OK;
 }
@@ -1558,6 +1561,11 @@ int32_t bh_set_option(const char* key, int64_t value) {
         return BH_OK;
     }
     if (!strcmp(key, "cauchy_fused")) { g_ctx.opt_cauchy_fused = value ? 1 : 0; return BH_OK; }
+    if (!strcmp(key, "cauchy_block")) {
+        if (!cauchy_block_value_ok(value)) return fail(BH_ERR_INVALID_ARG, "cauchy_block is 0, 1, 2, 4, 8 or 16 breakpoints per launch");
+        g_ctx.opt_cauchy_block = value;
+        return BH_OK;
+    }
     if (!strcmp(key, "linv_refine")) { g_ctx.opt_linv_refine = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "cauchy_gemm")) { g_ctx.opt_cauchy_gemm = value ? 1 : 0; return BH_OK; }
     if (!strcmp(key, "cauchy_image_max_ma")) { g_ctx.opt_cauchy_image_max_ma = std::min<int64_t>(std::max<int64_t>(0, value), 64); return BH_OK; }
@@ -2146,7 +2154,7 @@ int32_t bh_hess_destroy(bh_hess* H) {
     image_release(H->Jd, H->Jd_doubles);
     image_release(H->Jf, H->Jf_doubles);                          // (the stream is drained: no launch still reads the compact image)
     dev_free(H->fi_map); dev_free(H->fi_ops);
-    dev_free(H->vpad); dev_free(H->zpad); dev_free(H->upad); dev_free(H->tbuf); dev_free(H->timg); dev_free(H->timg_gen);
+    dev_free(H->vpad); dev_free(H->zpad); dev_free(H->upad); dev_free(H->tbuf); dev_free(H->timg); dev_free(H->timg_gen); dev_free(H->cblk);
     dev_free(H->partials); dev_free(H->sq_partials); dev_free(H->scalar);
     dev_free(H->G); dev_free(H->gpart); dev_free(H->geq);
     for (auto e : H->ev) if (e) (void)hipEventDestroy(e);
@@ -3455,6 +3463,7 @@ constexpr int kDowndateRefresh = 8;     // chol_downdate = 1: breakpoints betwee
 
 struct CauchyPlan {
     CauchyForm form = CAUCHY_SWEEP; bool fused = false; int refresh = 0;   // the selection (bh_cauchy_plan.h)
+    int block = 0;                  // ... and the effective cauchy_block: K >= 2 breakpoints per launch of the one-kernel form, else 0
     bool gemm = false;              // row space with equalities: B = J~ D A' by image_b_mfma_kernel (else mA J v sweeps)
     bool gen_tiled = false;         // ... and its row body in tiles of 64 rows (few equalities: one row per thread, see bh_cauchy.hip.h)
     bool factor_downdate = false;   // sweeping form: rank-one downdates of the factor itself
@@ -3480,6 +3489,9 @@ struct CauchyRun {
     CauchyPass* pp = nullptr;
     double* part_pp[2] = {nullptr, nullptr};
     double* sbuf[2] = {nullptr, nullptr};   // s_c ping-pong of the fused form (H*d is never formed there)
+    double* sbuf3 = nullptr;                // option cauchy_block: the third s_c buffer, the records and the K-deep partial sums
+    CauchyBlockRec* brec = nullptr;
+    double* bpart[2] = {nullptr, nullptr};
     int reform_sweeps = 0;          // sweeps over J of one re-formation, for stats.n_jv
 };
 
@@ -3491,9 +3503,10 @@ static CauchyPlan cauchy_make_plan(const bh_hess* H, const bh_proj* P) {
     in.multi_panel = multi_panel(H); in.last_cauchy_passes = P->last_cauchy_passes;
     in.cauchy_image = g_ctx.opt_cauchy_image; in.cauchy_image_max_ma = g_ctx.opt_cauchy_image_max_ma; in.cauchy_fused = g_ctx.opt_cauchy_fused;
     in.cauchy_gram = g_ctx.opt_cauchy_gram; in.cauchy_gram_eq = g_ctx.opt_cauchy_gram_eq; in.cauchy_image_refresh = g_ctx.opt_cauchy_image_refresh;
+    in.n = H->n; in.cauchy_block = g_ctx.opt_cauchy_block;
     const CauchySelection sel = cauchy_select(in);
     CauchyPlan p;
-    p.form = sel.form; p.fused = sel.fused; p.refresh = sel.refresh;
+    p.form = sel.form; p.fused = sel.fused; p.refresh = sel.refresh; p.block = sel.block;
     // B = J~ D A' (rows x mA): ONE sweep on the matrix cores (image_b_mfma_kernel) when the images share their leading dimension,
     // else mA J v sweeps over masked rows of A
     p.gemm = g_ctx.opt_cauchy_gemm != 0 && P->ldA == H->ld;
@@ -3518,6 +3531,14 @@ static CauchyPlan cauchy_make_plan(const bh_hess* H, const bh_proj* P) {
     p.sched.off = p.fused ? 1 : 0;
     p.sched.max_units = p.max_pass + p.sched.off; p.sched.first = 2 + p.sched.off;
     p.sched.await_iter = false; p.sched.lock_step = true; p.sched.look_first = false;
+    // K breakpoints per launch: unit 0 is launch 0, block launch 1 takes decision 0, every later one K decisions (the wait callable
+    // translates unit targets into passes: cauchy_block_pass_target); one rank only, so decisions follow `done` as seen
+    // (a unit of K passes: four of them queued keep the GPU as busy as eight single passes; batch <= first keeps the units
+    // enqueued behind the end of a search below first + batch, whenever the host happens to look: tests/test_cauchy_block_cpu.py)
+    if (p.block > 0) {
+        p.sched.max_units = 2 + (p.max_pass + p.block - 1) / p.block; p.sched.lock_step = false;
+        p.sched.first = 3 + p.sched.off; p.sched.batch = 4;
+    }
     return p;
 }
 
@@ -3552,6 +3573,16 @@ static int32_t cauchy_ensure_buffers(CauchyRun& r) {
         r.pp = reinterpret_cast<CauchyPass*>(r.img_scal + 8);     // 2 x 32 bytes in the 16-double tail of timg
         r.part_pp[0] = H->timg + 2 * img_cap; r.part_pp[1] = r.part_pp[0] + 2 * kCauchyFusedGrid;
         r.a.fixpass = reinterpret_cast<int*>(r.c.v); r.a.pp0 = r.pp;
+    }
+    if (r.plan.block > 0) {
+        // (sized for any K and any width the rule admits: allocated once per handle)
+        constexpr int64_t rec_doubles = (2 * (int64_t)sizeof(CauchyBlockRec) + 7) / 8;
+        const int64_t part_doubles = (int64_t)kCauchyBlockMaxK * 2 * kCauchyFusedGrid;
+        if (!H->cblk) BH_TRY(dev_alloc(&H->cblk, kCauchyBlockMaxN + rec_doubles + 2 * part_doubles));
+        r.sbuf3 = H->cblk;
+        r.brec = reinterpret_cast<CauchyBlockRec*>(H->cblk + kCauchyBlockMaxN);
+        r.bpart[0] = H->cblk + kCauchyBlockMaxN + rec_doubles; r.bpart[1] = r.bpart[0] + part_doubles;
+        r.a.pp0 = reinterpret_cast<CauchyPass*>(r.brec);          // cauchy_init_kernel writes the first five words of record 0
     }
     return BH_OK;
 }
@@ -3685,6 +3716,32 @@ static int32_t cauchy_pass_rowspace_fused(CauchyRun& r, int index) {
     return BH_OK;
 }
 
+// Form 1, K breakpoints per launch (option cauchy_block): launch 0 as above; block launch b >= 1 verifies the decisions block b-1 ran
+// ahead of, then runs K passes ahead itself (cauchy_block_kernel<K>, bh_cauchyblock.hip.h).
+static int32_t cauchy_pass_rowspace_block(CauchyRun& r, int index) {
+    bh_hess* H = r.H; hipStream_t s = r.s;
+    const CauchyPlan& p = r.plan;
+    const CauchyArgs& a = r.a;
+    if (index == 0) return cauchy_pass_rowspace_fused(r, 0);
+    CauchyBlockArgs ba{};
+    ba.rec = r.brec; ba.b = index; ba.g = a.g; ba.dl = a.dl; ba.du = a.du;
+    ba.sbuf[0] = r.sbuf[0]; ba.sbuf[1] = r.sbuf[1]; ba.sbuf[2] = r.sbuf3;
+    ba.fixpass = a.fixpass; ba.fixrank = r.P->fixrank; ba.n = a.n; ba.nmm = a.nmm;
+    ba.J = H->Jd; ba.ld = H->ld; ba.nrows = r.img_rows; ba.d_rows = H->d; ba.mu = H->mu;
+    ba.td = H->timg; ba.ts = H->timg + r.img_cap;
+    ba.part_in = index == 1 ? r.part_pp[0] : r.bpart[(index - 1) & 1]; ba.Gin = index == 1 ? p.img_grid : p.fused_grid;
+    ba.part_out = r.bpart[index & 1];
+    ba.mirror = a.mirror; ba.tag = a.tag;
+    switch (p.block) {
+        case 2: hipLaunchKernelGGL(cauchy_block_kernel<2>, dim3(p.fused_grid), dim3(CA_T), 0, s, ba); break;
+        case 4: hipLaunchKernelGGL(cauchy_block_kernel<4>, dim3(p.fused_grid), dim3(CA_T), 0, s, ba); break;
+        case 8: hipLaunchKernelGGL(cauchy_block_kernel<8>, dim3(p.fused_grid), dim3(CA_T), 0, s, ba); break;
+        default: hipLaunchKernelGGL(cauchy_block_kernel<16>, dim3(p.fused_grid), dim3(CA_T), 0, s, ba); break;
+    }
+    BH_HIP(hipGetLastError());
+    return BH_OK;
+}
+
 // Form 2.  Three launches per pass (mA <= 64): [downdate + refactorisation + right-hand side + the two solves: y]
 // -> [rows | d = P(-g) | t_fresh = A_free(-g) for the next pass] -> [decision]
 static int32_t cauchy_pass_rowspace_eq(CauchyRun& r, int index) {
@@ -3760,7 +3817,8 @@ static int32_t cauchy_pass_gram_eq(CauchyRun& r, int index) {
 
 static int32_t cauchy_launch_pass(CauchyRun& r, int index) {
     switch (r.plan.form) {
-        case CAUCHY_ROWSPACE_BOX: return r.plan.fused ? cauchy_pass_rowspace_fused(r, index) : cauchy_pass_rowspace_box(r, index);
+        case CAUCHY_ROWSPACE_BOX:
+            return r.plan.block > 0 ? cauchy_pass_rowspace_block(r, index) : r.plan.fused ? cauchy_pass_rowspace_fused(r, index) : cauchy_pass_rowspace_box(r, index);
         case CAUCHY_ROWSPACE_EQ: return cauchy_pass_rowspace_eq(r, index);
         case CAUCHY_GRAM_EQ: return cauchy_pass_gram_eq(r, index);
         default: return cauchy_pass_sweep(r, index);               // (CAUCHY_GRAM has no passes: one launch, see cauchy_impl)
@@ -3845,10 +3903,21 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
         // The launch-ahead schedule of bh_launch_ahead.h, lock-step (mirror: status field = error flag, iter field = breakpoints,
         // n_hmul = passes run).
         BH_TRY(launch_ahead(plan.sched, [&](int index) { return cauchy_launch_pass(run, index); },
-                            [&](int n_hmul_target, int iter_target, MirrorWord* m) { return wait_mirror(c, a.tag, n_hmul_target, m, iter_target); }, &mw));
+                            [&](int n_hmul_target, int iter_target, MirrorWord* m) {
+                                const int passes = plan.block > 0 ? cauchy_block_pass_target(n_hmul_target, plan.block) : n_hmul_target;
+                                return wait_mirror(c, a.tag, passes, m, iter_target);
+                            }, &mw));
     }
-    // (fused form: decision j is taken by launch j+1, which writes s_c into buffer (j+1) & 1)
-    BH_TRY(fetch_vec(s_out, plan.fused ? run.sbuf[mw.n_hmul & 1] : c.w, n, dev));
+    // (fused form: decision j is taken by launch j+1, which writes s_c into buffer (j+1) & 1; K breakpoints per launch: the block
+    // launch that took the last decision wrote it into buffer (launch mod 3))
+    const double* s_final = c.w;
+    if (plan.block > 0) {
+        const int bl = cauchy_block_final_launch(mw.n_hmul, plan.block) % 3;
+        s_final = bl == 2 ? run.sbuf3 : run.sbuf[bl];
+    } else if (plan.fused) {
+        s_final = run.sbuf[mw.n_hmul & 1];
+    }
+    BH_TRY(fetch_vec(s_out, s_final, n, dev));
     int info_host = 0;
     BH_TRY(adopt_device_mask(P, fix_chunks_out, &info_host));     // drains the stream; canonical fixrank / fixidx, P->nfix
     cauchy_account(run, mw, launches_in);

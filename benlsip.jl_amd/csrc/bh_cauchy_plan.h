@@ -24,17 +24,23 @@ struct CauchySelectIn {
     bool multi_panel;             // J is wider than the register-resident kernels hold (n > 16384)
     int last_cauchy_passes;       // passes of the previous search on this bh_proj (-1: none yet)
     int64_t cauchy_image, cauchy_image_max_ma, cauchy_fused, cauchy_gram, cauchy_gram_eq, cauchy_image_refresh;   // the options
+    int64_t n;                    // columns of J (the blocked search keeps the whole vector side in registers: n <= 4096)
+    int64_t cauchy_block;         // option cauchy_block = K: breakpoints per launch of the one-kernel row-space search (0, 1: one)
 };
 
 struct CauchySelection {
     CauchyForm form;
     bool fused;                   // row space, box: ONE kernel per breakpoint (cauchy_fused_kernel)
     int refresh;                  // effective cauchy_image_refresh: 0, or the interval R clamped to the 20-bit pass counter
+    int block;                    // effective cauchy_block: 0, or K >= 2 breakpoints per launch (cauchy_block_kernel<K>)
 };
+
+// The vector side of cauchy_block_kernel lives in registers: 8 elements in each of 512 threads.
+constexpr int64_t kCauchyBlockMaxN = 4096;
 
 inline CauchySelection cauchy_select(const CauchySelectIn& in) {
     const int mA = in.mA;
-    CauchySelection o{CAUCHY_SWEEP, false, 0};
+    CauchySelection o{CAUCHY_SWEEP, false, 0, 0};
     // Gram-form handle, box constraints, one rank, option "cauchy_gram": init -> G d -> cauchy_gram_kernel, the whole search in one
     // launch (bh_cauchygram.hip.h).  Any other case takes the path it takes without the option.
     if (in.cauchy_gram != 0 && in.gram_handle && mA == 0 && !in.comm) o.form = CAUCHY_GRAM;
@@ -59,7 +65,20 @@ inline CauchySelection cauchy_select(const CauchySelectIn& in) {
     //   two-kernel box form:       [J v of d] [J v of s_c] before cauchy_image_kernel(fresh = 1)
     //   with equalities:           [mask g, J v: a] [B: the GEMM or mA masked sweeps] [J v of s_c] before the row kernel (fresh = 1)
     if (image && !in.comm && !(o.fused && in.multi_panel)) o.refresh = (int)std::min<int64_t>(in.cauchy_image_refresh, 0xfffff);
+    // Option cauchy_block = K >= 2: the one-kernel form takes K breakpoints per launch (bh_cauchyblock.hip.h) — box constraints, one
+    // rank, no re-formation of the images, the whole vector in the registers of one workgroup.  Any other case: the path of K = 0.
+    if (o.form == CAUCHY_ROWSPACE_BOX && o.fused && !in.comm && o.refresh == 0 && in.n <= kCauchyBlockMaxN && in.cauchy_block >= 2)
+        o.block = (int)in.cauchy_block;
     return o;
 }
+
+// The values option cauchy_block accepts (0 and 1: the one-breakpoint-per-launch path).
+inline bool cauchy_block_value_ok(int64_t v) { return v == 0 || v == 1 || v == 2 || v == 4 || v == 8 || v == 16; }
+
+// The blocked search on the launch-ahead schedule (off = 1: unit 0 is launch 0, unit b >= 1 is block launch b).  Block launch 1
+// takes decision 0, every later one the K decisions behind it: once `unit_target` units have spoken, this many passes are decided.
+inline int cauchy_block_pass_target(int unit_target, int K) { return unit_target <= 0 ? 0 : 1 + (unit_target - 1) * K; }
+// The block launch that took the last of `passes` decisions — it wrote the final s_c into buffer (launch mod 3).
+inline int cauchy_block_final_launch(int passes, int K) { return 1 + (std::max(passes, 1) - 1 + K - 1) / K; }
 
 }  // namespace bh

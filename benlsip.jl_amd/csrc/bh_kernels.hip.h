@@ -23,6 +23,7 @@
 #include "bh_cgfuse.hip.h"
 #include "bh_proj.hip.h"
 #include "bh_cauchy.hip.h"
+#include "bh_cauchyblock.hip.h"
 #include "bh_cauchygram.hip.h"
 #include "bh_cauchygrameq.hip.h"
 #include "bh_minor.hip.h"

@@ -514,7 +514,8 @@ def set_option(key, value):
     ``proj_form``, ``cauchy_image``, ``cauchy_gram``, ``cauchy_gram_eq`` (Cauchy search with 1..64 linear equalities from ``G`` on a
     Gram-form handle, default 0), ``gram_cg_fused`` (fused two- / three-kernel CG iteration on a Gram-form handle, default 0) and
     ``cauchy_image_refresh`` (row-space Cauchy search on one rank: R >= 1 forms the carried images again from ``J`` every R-th pass,
-    default 0 = never), ``gram_ingest`` (``AlHessian.create_async`` builds ``G`` during the upload and returns a Gram-form handle,
+    default 0 = never), ``cauchy_block`` (that search with box constraints on one rank, n <= 4096: K = 2, 4, 8 or 16 breakpoints per
+    launch, bit-identical to the default 0), ``gram_ingest`` (``AlHessian.create_async`` builds ``G`` during the upload and returns a Gram-form handle,
     default 0) and ``free_image_minor`` (``minor_iterate`` with ``ls_from_cg`` = 1 and ``step_from_cg`` = 0 may run its CG loop and its
     line search on the compact image of the free columns under the rules of ``free_image``, default 0)."""
     check(_lib.lib().bh_set_option(key.encode(), int(value)), "bh_set_option(%s)" % key)

@@ -427,6 +427,17 @@ int32_t bh_stats_reset(bh_hess* H);
  *                        (the passes) and n_breakpoints keep their meaning, bh_cauchy_info's form too (its launch count includes the
  *                        extra launches).  Several ranks: ignored, the path is exactly the one without the option.
  *                        A negative value: BH_ERR_INVALID_ARG
+ *   "cauchy_block"   [0] that search with "cauchy_fused" = 1 (box constraints, one rank, "cauchy_image_refresh" = 0, n <= 4096): K = 2, 4,
+ *                        8 or 16 breakpoints per launch.  With box constraints the row update of a pass needs only theta and the index
+ *                        fixed, which follow from the n-vectors; the two sums merely decide whether the search stops there.  So a
+ *                        launch runs K advances ahead (cauchy_block_kernel<K>: K column updates of its rows from registers, K pairs of
+ *                        partial sums) and the next launch checks the K decisions in order; at most K - 1 advances are thrown away,
+ *                        once, at the end.  Same operations in the same order per row and per sum: the step, the active set, n_hmul
+ *                        (passes), n_breakpoints and stats.n_jv (+ 1) are those of 0, bit for bit; bh_cauchy_info reports form 1 and
+ *                        about passes / K + 2 launches of the search instead of passes + 1.  0, 1 = one breakpoint per launch; any
+ *                        other case (equalities, several ranks, "cauchy_fused" = 0, a re-formation interval, n > 4096, a Gram-form
+ *                        search) takes exactly the path it takes with 0.  Any other value: BH_ERR_INVALID_ARG, the option keeps its
+ *                        value.  Environment: BH_CAUCHY_BLOCK (read by bh_init; a value outside the list is ignored)
  *   "cauchy_gram"    [0] bh_cauchy_step(_dev) on a handle in the Gram form (bh_hess_set_form), no linear equalities, one rank: the whole
  *                        search in ONE launch from G (init -> G d -> cauchy_gram_kernel: Hd downdated by one row of G per breakpoint, the
  *                        loop runs on the device; the launch count does not depend on the number of breakpoints).  Any other handle or
