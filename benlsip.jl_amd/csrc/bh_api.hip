@@ -8,6 +8,7 @@
 #include "bh_kernels.hip.h"
 #include "bh_launch_ahead.h"
 #include "bh_pcg_plan.h"
+#include "bh_step_chain_plan.h"
 
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -51,7 +52,7 @@ struct CgWorkspace {
     double *w = nullptr, *r = nullptr, *v = nullptr, *p = nullptr, *Hp = nullptr, *g = nullptr, *wl = nullptr, *wu = nullptr;
     double *x = nullptr, *s = nullptr, *xlow = nullptr, *xupp = nullptr;   // minor_iterate staging
     double* hw = nullptr;          // H*w accumulated by the CG loop for minor_iterate's linesearch
-    double* hwc = nullptr;         // ... its free part in slot order, when that loop ran on the compact image (option free_image_minor)
+    double* hwc = nullptr;         // ... its free part in slot order, when that loop ran on the compact image (options free_image_minor, free_image_chain)
     double *p2 = nullptr, *gpart = nullptr, *rvpart = nullptr;   // two-kernel box iteration: p ping-pong, (spare), r.v partials (2 x n_pad/2)
     double *r2 = nullptr, *hpx = nullptr, *hpx_tail = nullptr;   // RCCL form of it: r ping-pong; H*p with the p'Hp slot right behind it (hpx[n_pad] = hpx_tail[0])
     double* slab = nullptr;
@@ -151,7 +152,9 @@ struct Ctx {
     struct { const void* H = nullptr; const double* w = nullptr; const double* gm = nullptr; } hw_note;   // what cg.hw currently is H*w of
     // the last (H, s, g, g_minor) for which the library itself wrote g_minor = H*s + g (bh_hmul_add_dev, bh_step_accumulate_dev):
     // with step_from_cg on, bh_model_reduction_dev on the same H, s, g takes s'Hs = s.(g_minor - g) instead of sweeping J
-    struct { const void* H = nullptr; const double* s = nullptr; const double* g = nullptr; const double* gm = nullptr; } gm_note;
+    // fixed_part_stale, q_valid: the chain of steps behind option free_image_chain (bh_step_chain_plan.h)
+    struct { const void* H = nullptr; const double* s = nullptr; const double* g = nullptr; const double* gm = nullptr;
+             bool fixed_part_stale = false, q_valid = false; } gm_note;
     int64_t opt_fold_init = 1;       // box CG: fold the initialisation into the first H*p / step launches
     int64_t opt_final_sync = 0;      // *_dev: always drain the stream before returning (1), or only wait for what the host is owed (0)
     int64_t opt_host_copy_kernels = 1;   // host vectors of the host-pointer entry points: copy kernels on the mapped pinned arena (1) or DMA (0)
@@ -162,6 +165,12 @@ struct Ctx {
     // bh_minor_iterate* with ls_from_cg = 1 and step_from_cg = 0: the call is considered for the compact image like a bh_pcg* (the
     // loop accumulates the free part of H*w, free_image_linesearch_kernel takes the line search on the compact operands); 0: never
     int64_t opt_free_image_minor = 0;
+    // the same with step_from_cg = 1, the resident inner-step chain: the line search keeps cg.hwc scaled with w, bh_step_accumulate_dev
+    // adds it to g_minor on the free variables only and carries the model value q(s) in cg.scalars[kStepQSlot], which
+    // bh_model_reduction_dev then returns — no sweep over J anywhere in the chain; 0: such calls stay on the full image
+    int64_t opt_free_image_chain = 0;
+    // after such a call: cg.hwc, the compact w (cg.s) and H->fi_map (nfree slots) describe the call that delivered w for g_minor = gm
+    struct { const void* H = nullptr; const double* w = nullptr; const double* gm = nullptr; int64_t nfree = 0; } hwc_note;
     int64_t opt_gram_ingest = 0;     // bh_hess_create_async, one rank, n <= 16384: the handle is born in the Gram form, G built during the upload
     int64_t opt_ev_stride = 8;       // BH_FLAG_PROFILE: hipEvents around every opt_ev_stride-th H*p launch of a handle
     // RCCL
@@ -518,7 +527,9 @@ int32_t ensure_cg_workspace(int64_t n_pad, int64_t trace_cap) {
         constexpr int NV = 20;
         dev_free(c.slab);
         c.slab = nullptr;
-        g_ctx.hw_note = {};                      // cg.hw and cg.hwc go with the old slab
+        g_ctx.hw_note = {};                      // cg.hw and cg.hwc go with the old slab ...
+        g_ctx.hwc_note = {};
+        g_ctx.gm_note.q_valid = false;           // ... and so does the carried q (cg.scalars)
         BH_TRY(dev_alloc(&c.slab, NV * n_pad + 8));
         BH_HIP(hipMemsetAsync(c.slab, 0, (size_t)(NV * n_pad + 8) * sizeof(double), g_ctx.stream));
         for (int i = 0; i < NV; ++i) *vecs[i] = c.slab + (int64_t)i * n_pad;
@@ -1483,6 +1494,8 @@ int32_t bh_shutdown(void) {
     dev_free(c.slab); dev_free(c.d_state); dev_free(c.d_trace); dev_free(c.d_reroute);
     if (c.h_mirror) (void)hipHostFree(const_cast<unsigned long long*>(c.h_mirror));
     c = CgWorkspace();
+    g_ctx.hwc_note = {};
+    g_ctx.gm_note.q_valid = false;
     dev_free(g_ctx.scratch_dev); g_ctx.scratch_dev = nullptr;
     dev_free(g_ctx.rbuf); g_ctx.rbuf = nullptr; g_ctx.rbuf_cap = 0;
     if (g_ctx.mbox_h) { (void)hipHostFree(const_cast<unsigned long long*>(g_ctx.mbox_h)); g_ctx.mbox_h = nullptr; g_ctx.mbox_d = nullptr; }
@@ -1583,6 +1596,11 @@ int32_t bh_set_option(const char* key, int64_t value) {
     if (!strcmp(key, "free_image_minor")) {
         if (value != 0 && value != 1) return fail(BH_ERR_INVALID_ARG, "free_image_minor is 0 or 1");
         g_ctx.opt_free_image_minor = value;
+        return BH_OK;
+    }
+    if (!strcmp(key, "free_image_chain")) {
+        if (value != 0 && value != 1) return fail(BH_ERR_INVALID_ARG, "free_image_chain is 0 or 1");
+        g_ctx.opt_free_image_chain = value;
         return BH_OK;
     }
     if (!strcmp(key, "gram_ingest")) {
@@ -2037,6 +2055,8 @@ int32_t bh_hess_set_mu(bh_hess* H, double mu) {
     if (mu == H->mu) return BH_OK;          // the Julia shim calls this on every handle(H): never a rebuild
     H->mu = mu;
     H->G_valid = false;                      // Gram form: rebuilt before the next product that reads G
+    if (g_ctx.hwc_note.H == H) g_ctx.hwc_note = {};                        // cg.hwc is H*w of the old mu ...
+    if (g_ctx.gm_note.H == H) g_ctx.gm_note.q_valid = false;               // ... and the carried q its model value
     return BH_OK;
 }
 
@@ -2064,6 +2084,7 @@ static int32_t gram_enter(bh_hess* H) {
     H->stats.bytes_per_hmul = hmul_bytes(H);
     H->timed_bytes = 0.0; H->timed_n = 0;
     if (g_ctx.hw_note.H == H) g_ctx.hw_note = {};
+    if (g_ctx.hwc_note.H == H) g_ctx.hwc_note = {};
     if (g_ctx.gm_note.H == H) g_ctx.gm_note = {};
     return BH_OK;
 }
@@ -2085,6 +2106,7 @@ int32_t bh_hess_set_form(bh_hess* H, int32_t form) {
     H->stats.bytes_per_hmul = hmul_bytes(H);
     H->timed_bytes = 0.0; H->timed_n = 0;
     if (g_ctx.hw_note.H == H) g_ctx.hw_note = {};
+    if (g_ctx.hwc_note.H == H) g_ctx.hwc_note = {};
     if (g_ctx.gm_note.H == H) g_ctx.gm_note = {};
     return rc;
 }
@@ -2141,6 +2163,7 @@ int32_t bh_hess_free_image_read(bh_hess* H, double* image_out, int64_t image_cap
 
 int32_t bh_hess_destroy(bh_hess* H) {
     if (H && g_ctx.hw_note.H == H) g_ctx.hw_note = {};
+    if (H && g_ctx.hwc_note.H == H) g_ctx.hwc_note = {};
     if (H && g_ctx.gm_note.H == H) g_ctx.gm_note = {};
     if (!H) return BH_OK;
     if (H->up) {                              // an upload still in flight: let it finish before its buffers go
@@ -2468,6 +2491,7 @@ static int launch_batch_size(const bh_hess* H) {
 // ---- compact image of the free columns (option free_image) ----------------------------------
 // Jf goes back to the image pool.  (Launches that read it may be queued: the stream is drained first.)
 static void free_image_release(bh_hess* H) {
+    if (g_ctx.hwc_note.H == H) g_ctx.hwc_note = {};          // the map goes with the image
     if (H->Jf) {
         if (g_ctx.init) (void)hipStreamSynchronize(g_ctx.stream);
         image_release(H->Jf, H->Jf_doubles);
@@ -2508,6 +2532,7 @@ static int32_t free_image_prepare(bh_hess* H, bh_proj* P, bool* use, bool* earns
     }
     if (act == FI_USE) { H->fi_epoch = P->mask_epoch; b.served += 1; *use = true; return BH_OK; }        // an identical mask pushed again
     if (act == FI_MOVE) {
+        if (g_ctx.hwc_note.H == H) g_ctx.hwc_note = {};      // the slots change hands
         free_image_book_move(b, want, H->fi_ops_h);
         const int k = (int)H->fi_ops_h.size();
         count_h2d((size_t)k * sizeof(int));
@@ -2530,6 +2555,7 @@ static int32_t free_image_prepare(bh_hess* H, bh_proj* P, bool* use, bool* earns
             return BH_OK;
         }
     }
+    if (g_ctx.hwc_note.H == H) g_ctx.hwc_note = {};
     free_image_book_build(b, want, n);
     b.present = false;                                       // until the image exists
     const int64_t need = std::max<int64_t>(nrows, 1) * b.ldf;
@@ -2876,7 +2902,7 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
                        double kappa2, double atol_negcurv, double atol_f2b, int64_t trace_cap, PcgFin* fin_out, double* hw = nullptr,
                        bool g_pad_zeroed = false /* the staged copy of g arrived with its padding already zero */,
                        bool allow_free_image = true /* false: the compact loop handed this call back (bh_freeimg.hip.h) */,
-                       bool hw_free_part_ok = false /* nothing reads hw on the fixed variables (option free_image_minor) */) {
+                       bool hw_free_part_ok = false /* nothing reads hw on the fixed variables (options free_image_minor, free_image_chain) */) {
     const int64_t n = H->n, n_pad = H->ld;
     const int64_t max_iter64 = 2 * (n - P->mA - P->nfix);   // src/basic_tralcnlss.jl:714
     if (max_iter64 < 0) return fail(BH_ERR_PRECONDITION, "n - mA - count(fixvars) < 0");
@@ -2884,6 +2910,7 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
     CgWorkspace& c = g_ctx.cg;
     H->ev_pending.clear();
     if (hw != nullptr) g_ctx.hw_note = {};          // cg.hw is about to be overwritten
+    g_ctx.hwc_note = {};                            // any loop may run on the compact image: its gather rewrites the compact operands
     H->call_bytes = hmul_bytes(H);
 
     PcgRun run{H, P, c, g_ctx.stream};
@@ -3140,6 +3167,7 @@ static int32_t minor_iterate_impl(bh_hess* H, bh_proj* P, const double* x, const
     // instead of another sweep over J (-0.3 ms per minor iterate at config 3); mathematically identical, rounding ~1e-15.
     double* hw = g_ctx.opt_ls_from_cg ? c.hw : nullptr;
     if (!dev) {
+        g_ctx.hwc_note = {};                                                         // (the compact operands live in these vectors)
         BH_TRY(stage_vecs(c.s, {s_vec, x, xlow, xupp, g_model}, n, c.n_pad));      // c.s, c.x, c.xlow, c.xupp, c.g are consecutive
         xp = c.x; sp = c.s; lop = c.xlow; upp = c.xupp;
         BH_TRY(mbox_ensure());
@@ -3158,12 +3186,20 @@ static int32_t minor_iterate_impl(bh_hess* H, bh_proj* P, const double* x, const
     PcgFin fin{};
     // free_image_minor: with step_from_cg off the line search's w'Hw is the only consumer of hw, and w is zero on the fixed
     // variables — the free part of H*w is enough, so the loop may run on the compact image
-    const bool hw_free_part_ok = hw != nullptr && g_ctx.opt_free_image_minor == 1 && g_ctx.opt_step_from_cg == 0;
+    // free_image_chain: with step_from_cg on, bh_step_accumulate_dev takes the free part too (the fixed part of g_minor is read by
+    // nothing inside an inner step, and the model value is carried: bh_step_chain_plan.h)
+    const bool chain = g_ctx.opt_free_image_chain == 1 && g_ctx.opt_step_from_cg == 1;
+    const bool hw_free_part_ok = hw != nullptr && ((g_ctx.opt_free_image_minor == 1 && g_ctx.opt_step_from_cg == 0) || chain);
     BH_TRY(pcg_run(H, P, gp, c.wl, c.wu, wp, wp == c.w, kappa2, atol_negcurv, atol_f2b, 0, &fin, hw, !dev, true, hw_free_part_ok));
     double alpha = std::nan("");
     const bool do_ls = fin.status != BH_CG_NEGATIVE_CURVATURE;       // :669
     // alpha is written by the line search straight into the host-mapped mailbox (no DMA of its own)
-    if (do_ls && fin.compact && hw_free_part_ok) {
+    if (do_ls && fin.compact && hw_free_part_ok && chain) {
+        // ... and hwc scaled with w, for the accumulate that follows
+        hipLaunchKernelGGL(free_image_linesearch_scale_hw_kernel, dim3(1), dim3(CG_T), 0, g_ctx.stream, (const double*)c.x, c.s, (const double*)c.xlow,
+                           (const double*)c.xupp, c.hwc, (const int*)H->fi_map, wp, (int)H->fi.nfree, mbox_dev<double>(kMbScal));
+        BH_HIP(hipGetLastError());
+    } else if (do_ls && fin.compact && hw_free_part_ok) {
         // the compact operands the loop left (pcg_use_free_image): g, w, w_l, w_u in slot order and the free part of H*w
         hipLaunchKernelGGL(free_image_linesearch_kernel, dim3(1), dim3(CG_T), 0, g_ctx.stream, (const double*)c.x, c.s, (const double*)c.xlow,
                            (const double*)c.xupp, (const double*)c.hwc, (const int*)H->fi_map, wp, (int)H->fi.nfree, mbox_dev<double>(kMbScal));
@@ -3185,6 +3221,8 @@ static int32_t minor_iterate_impl(bh_hess* H, bh_proj* P, const double* x, const
     // cg.hw now holds H*w for the w just delivered (scaled with it by the line search): bh_step_accumulate_dev may use it.
     // Not after a loop on the compact image: that one left the free part of H*w in cg.hwc and cg.hw as it was.
     if (dev && hw != nullptr && !fin.compact) { g_ctx.hw_note.H = H; g_ctx.hw_note.w = w_out; g_ctx.hw_note.gm = g_model; }
+    // In the chain cg.hwc is that H*w on the free variables, in slot order beside the compact w (cg.s) and the handle's map.
+    if (dev && hw != nullptr && fin.compact && chain) g_ctx.hwc_note = {H, w_out, g_model, H->fi.nfree};
     if (status) *status = fin.status;
     if (iters) *iters = fin.iter;
     if (n_hmul_out) *n_hmul_out = fin.n_hmul;
@@ -3281,20 +3319,48 @@ int32_t bh_step_accumulate_dev(bh_hess* H, double* s_dev, const double* w_dev, c
     // The inner step's pattern (src/basic_tralcnlss.jl:434-437): g_minor_out holds H*s + g, it was the g_model of the
     // bh_minor_iterate_dev that has just produced w, and that call's CG loop accumulated H*w.  Then H*(s + w) + g = g_minor + H*w:
     // two n-vector kernels instead of a sweep over J.  Recognised by the three pointers; anything else recomputes H*s + g.
-    if (g_ctx.init && H && g_dev && g_minor_out_dev && g_ctx.opt_step_from_cg && g_ctx.hw_note.H == H && g_ctx.hw_note.w == w_dev &&
-        g_ctx.hw_note.gm == g_minor_out_dev && g_ctx.cg.hw != nullptr) {
-        g_ctx.hw_note = {};                          // one use: s changes below, a second call with the same w is a different step
-        const int64_t n = H->n;
-        const int grid = std::max(1, std::min((int)((n + 255) / 256), 1024));
+    //
+    // Option free_image_chain: behind a minor iterate whose loop ran on the compact image the H*w at hand is its free part, in slot
+    // order (cg.hwc).  Then only the free entries of g_minor are brought up to date — AFTER SUCH A CALL g_minor_out HOLDS H*s + g ON
+    // THE FREE VARIABLES ONLY, its entries on the fixed variables keep the value they had (nothing inside an inner step reads them:
+    // the next CG loop and the reduced-gradient norm mask them, and the active set only grows while one J lives) — and the model
+    // value q(s) = g.s + s'Hs / 2, which bh_model_reduction_dev could no longer take from such a g_minor, is carried along by
+    // q(s + w) = q(s) + w.g_minor + w'Hw / 2 over the free slots.  Which path runs: step_acc_select (bh_step_chain_plan.h).
+    const bool ok = g_ctx.init && H && g_dev && g_minor_out_dev;
+    CgWorkspace& c = g_ctx.cg;
+    StepAccIn in{};
+    in.step_from_cg = g_ctx.opt_step_from_cg; in.free_image_chain = g_ctx.opt_free_image_chain;
+    in.full_note = ok && g_ctx.hw_note.H == H && g_ctx.hw_note.w == w_dev && g_ctx.hw_note.gm == g_minor_out_dev && c.hw != nullptr;
+    in.compact_note = ok && g_ctx.hwc_note.H == H && g_ctx.hwc_note.w == w_dev && g_ctx.hwc_note.gm == g_minor_out_dev && c.hwc != nullptr &&
+                      H->fi.present && H->fi_map != nullptr && H->fi.nfree == g_ctx.hwc_note.nfree;
+    in.gm_note_match = ok && g_ctx.gm_note.H == H && g_ctx.gm_note.s == s_dev && g_ctx.gm_note.g == g_dev && g_ctx.gm_note.gm == g_minor_out_dev;
+    in.fixed_part_stale = g_ctx.gm_note.fixed_part_stale; in.q_valid = g_ctx.gm_note.q_valid;
+    const StepAccPlan plan = step_acc_select(in);
+    g_ctx.hw_note = {};                              // one use: s changes below, a second call with the same w is a different step
+    g_ctx.hwc_note = {};
+    if (plan.path == STEP_ACC_SWEEP) return hmul_add_impl(H, s_dev, g_dev, g_minor_out_dev, true, w_dev, s_dev);
+    const int64_t n = H->n;
+    const int grid = std::max(1, std::min((int)((n + 255) / 256), 1024));
+    if (plan.path == STEP_ACC_FULL || plan.path == STEP_ACC_FULL_CARRY) {
+        if (plan.path == STEP_ACC_FULL_CARRY)        // (reads g_minor before it is updated)
+            hipLaunchKernelGGL(step_carry_q_kernel, dim3(1), dim3(CG_T), 0, g_ctx.stream, w_dev, (const double*)c.hw, (const double*)g_minor_out_dev,
+                               (int)n, c.scalars);
         hipLaunchKernelGGL(vec_add_kernel, dim3(grid), dim3(256), 0, g_ctx.stream, (const double*)s_dev, w_dev, s_dev, (int)n);
-        hipLaunchKernelGGL(vec_add_kernel, dim3(grid), dim3(256), 0, g_ctx.stream, (const double*)g_minor_out_dev, (const double*)g_ctx.cg.hw,
+        hipLaunchKernelGGL(vec_add_kernel, dim3(grid), dim3(256), 0, g_ctx.stream, (const double*)g_minor_out_dev, (const double*)c.hw,
                            g_minor_out_dev, (int)n);
-        BH_HIP(hipGetLastError());
-        g_ctx.gm_note = {H, s_dev, g_dev, g_minor_out_dev};
-        return finish_device_call();
+    } else {
+        // q0 = g.s + s.(g_minor - g) / 2 from the vectors while all of g_minor is still valid (s is read before it moves)
+        if (plan.q_init)
+            hipLaunchKernelGGL(model_from_gminor_kernel, dim3(1), dim3(CG_T), 0, g_ctx.stream, g_dev, (const double*)s_dev, (const double*)g_minor_out_dev,
+                               (int)n, c.scalars + 2);
+        hipLaunchKernelGGL(vec_add_kernel, dim3(grid), dim3(256), 0, g_ctx.stream, (const double*)s_dev, w_dev, s_dev, (int)n);
+        const int q_mode = plan.path != STEP_ACC_COMPACT_CARRY ? kStepQNone : plan.q_init ? kStepQInit : kStepQCarry;
+        hipLaunchKernelGGL(free_image_step_accumulate_kernel, dim3(1), dim3(CG_T), 0, g_ctx.stream, (const double*)c.s, (const double*)c.hwc,
+                           (const int*)H->fi_map, g_minor_out_dev, (int)H->fi.nfree, c.scalars, q_mode);
     }
-    g_ctx.hw_note = {};
-    return hmul_add_impl(H, s_dev, g_dev, g_minor_out_dev, true, w_dev, s_dev);
+    BH_HIP(hipGetLastError());
+    g_ctx.gm_note = {H, s_dev, g_dev, g_minor_out_dev, plan.fixed_part_stale, plan.q_valid};
+    return finish_device_call();
 }
 
 // active_indx = active_bounds(lincons, x, s, delta); add_active!(lincons, chol_aat, active_indx) — or, when mA + |active_indx| > n,
@@ -3388,7 +3454,17 @@ int32_t bh_model_reduction_dev(bh_hess* H, const double* g_dev, const double* s_
     if (!H || !g_dev || !s_dev || !out) return fail(BH_ERR_INVALID_ARG, "NULL argument");
     BH_TRY(ensure_cg_workspace(H->ld, 0));
     CgWorkspace& c = g_ctx.cg;
-    if (g_ctx.opt_step_from_cg && g_ctx.gm_note.H == H && g_ctx.gm_note.s == s_dev && g_ctx.gm_note.g == g_dev && g_ctx.gm_note.gm != nullptr) {
+    const bool note = g_ctx.gm_note.H == H && g_ctx.gm_note.s == s_dev && g_ctx.gm_note.g == g_dev && g_ctx.gm_note.gm != nullptr;
+    const ModelPath path = model_select(g_ctx.opt_step_from_cg, note, g_ctx.gm_note.fixed_part_stale, g_ctx.gm_note.q_valid);
+    if (path == MODEL_CARRIED) {
+        // a chain of steps under option free_image_chain: g_minor is stale on the fixed variables, q(s) was carried instead
+        // (bh_step_accumulate_dev) — it rides to the host with the seal, no launch of its own
+        BH_TRY(mbox_ensure());
+        BH_TRY(mbox_seal_and_wait(sizeof(double), c.scalars + kStepQSlot, nullptr, mbox_dev<double>(kMbScal)));
+        *out = mbox_host<double>(kMbScal)[0];
+        return BH_OK;
+    }
+    if (path == MODEL_FROM_GMINOR) {
         // the library wrote g_minor = H*s + g for exactly these vectors (and, by the caller's opt-in, nobody has touched them since):
         // s'Hs = s.(g_minor - g), g.s — no sweep over J (the rounding of the difference is that of g.s itself: eps |g||s|)
         hipLaunchKernelGGL(model_from_gminor_kernel, dim3(1), dim3(CG_T), 0, g_ctx.stream, g_dev, s_dev, g_ctx.gm_note.gm, (int)H->n, c.scalars + 2);
@@ -3867,6 +3943,7 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
         BH_TRY(ensure_trsv_lds(lds));
     }
     // (the Cauchy kernels read x, g and the bounds element by element: a device caller's vectors are used where they lie)
+    if (!dev) g_ctx.hwc_note = {};                                                  // (the compact operands of a minor iterate live in these vectors)
     if (!dev) BH_TRY(stage_vecs(c.x, {x, xlow, xupp, g}, n, c.n_pad));            // c.x, c.xlow, c.xupp, c.g are consecutive
 
     CauchyRun run{H, P, c, s};

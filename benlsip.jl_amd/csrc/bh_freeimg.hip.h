@@ -1,5 +1,6 @@
 // bh_freeimg.hip.h — the compact image of the free columns (option "free_image"): build, column moves, the gather in front
-// of the box-constrained CG loop that runs on it, and the line search behind it (option "free_image_minor")
+// of the box-constrained CG loop that runs on it, the line search behind it (option "free_image_minor") and the accumulate of the
+// resident inner-step chain behind that (option "free_image_chain")
 // Part of the single translation unit of bh_api.hip (see bh_kernels.hip.h for the layout and design notes).
 //
 // In the box-constrained CG loop every p_j is zero on the fixed variables, and their entries of H*p are used for nothing
@@ -110,19 +111,91 @@ __global__ __launch_bounds__(256) void free_image_gather_kernel(FreeGatherArgs a
 // The scaled w goes into the compact buffer and, from the same thread, into the caller's w at map[i]; alpha into out[0].
 // The caller's w keeps the +0 the gather wrote on the fixed variables: with a negative or non-finite alpha linesearch_kernel would
 // leave alpha * 0 there (-0 or NaN).  hw is not scaled: nothing reads it after this launch.
+template <bool SCALE_HW, typename HW>
+__device__ __forceinline__ void free_image_linesearch_body(const double* __restrict__ gc, double* __restrict__ wc, const double* __restrict__ wlc,
+                                                           const double* __restrict__ wuc, HW* __restrict__ hwc, const int* __restrict__ map,
+                                                           double* __restrict__ w_full, int nfree, double* __restrict__ out, double* scratch) {
+    const double alpha = linesearch_alpha(gc, wc, wlc, wuc, nullptr, nullptr, hwc, nfree, scratch);
+    for (int i = threadIdx.x; i < nfree; i += CG_T) {
+        const double wi = __dmul_rn(alpha, wc[i]);          // :671
+        wc[i] = wi;
+        if constexpr (SCALE_HW) hwc[i] = __dmul_rn(alpha, hwc[i]);
+        const int m = map[i];                                // (i < nfree: a column of the caller's w)
+        if (m >= 0) w_full[m] = wi;
+    }
+    if (threadIdx.x == 0) out[0] = alpha;
+}
+
 __global__ __launch_bounds__(CG_T) void free_image_linesearch_kernel(const double* __restrict__ gc, double* __restrict__ wc,
                                                                      const double* __restrict__ wlc, const double* __restrict__ wuc,
                                                                      const double* __restrict__ hwc, const int* __restrict__ map,
                                                                      double* __restrict__ w_full, int nfree, double* __restrict__ out) {
     __shared__ double scratch[2 * (CG_T / 64)];
-    const double alpha = linesearch_alpha(gc, wc, wlc, wuc, nullptr, nullptr, hwc, nfree, scratch);
-    for (int i = threadIdx.x; i < nfree; i += CG_T) {
-        const double wi = __dmul_rn(alpha, wc[i]);          // :671
-        wc[i] = wi;
-        const int m = map[i];                                // (i < nfree: a column of the caller's w)
-        if (m >= 0) w_full[m] = wi;
+    free_image_linesearch_body<false>(gc, wc, wlc, wuc, hwc, map, w_full, nfree, out, scratch);
+}
+
+// The same behind a compact loop of the resident inner-step chain (option "free_image_chain", step_from_cg = 1): the thread that
+// owns slot i also scales hwc[i], as linesearch_kernel does on the full vectors, so that hwc stays the free part of H*w for the
+// scaled w — free_image_step_accumulate_kernel adds it to g_minor.  alpha, w and the caller's w are those of the kernel above.
+__global__ __launch_bounds__(CG_T) void free_image_linesearch_scale_hw_kernel(const double* __restrict__ gc, double* __restrict__ wc,
+                                                                              const double* __restrict__ wlc, const double* __restrict__ wuc,
+                                                                              double* __restrict__ hwc, const int* __restrict__ map,
+                                                                              double* __restrict__ w_full, int nfree, double* __restrict__ out) {
+    __shared__ double scratch[2 * (CG_T / 64)];
+    free_image_linesearch_body<true>(gc, wc, wlc, wuc, hwc, map, w_full, nfree, out, scratch);
+}
+
+// The model value q(s) = g.s + s'Hs / 2 carried along a chain of steps s += w (options "step_from_cg" and "free_image_chain"):
+//   q(s + w) = q(s) + w.(H s + g) + w'Hw / 2 = q(s) + sum w_i gm_i + (sum w_i hw_i) / 2,   gm = H s + g BEFORE it is updated.
+// w is zero on the fixed variables, so the sums need the free entries only.  sc: the workspace scalars — sc[4] is q; with
+// q_mode = kStepQInit the chain has none yet and q(s) is formed from sc[2] = s.(gm - g), sc[3] = g.s, which
+// model_from_gminor_kernel left on the still fully valid gm (the host's g.s + 0.5 s'Hs of bh_model_reduction_dev).
+constexpr int kStepQNone = 0, kStepQCarry = 1, kStepQInit = 2;
+constexpr int kStepQSlot = 4;
+__device__ __forceinline__ void step_q_store(double* __restrict__ sc, int q_mode, double d1, double d2) {
+    const double q = (q_mode == kStepQInit) ? __dadd_rn(sc[3], __dmul_rn(0.5, sc[2])) : sc[kStepQSlot];
+    sc[kStepQSlot] = __dadd_rn(q, __dadd_rn(d1, __dmul_rn(0.5, d2)));
+}
+
+// bh_step_accumulate_dev behind a compact minor iterate of the chain: g_minor[map[c]] += hwc[c] over the nfree slots — the
+// per-element arithmetic of vec_add_kernel on the scaled H*w, on the free variables only (the entries of g_minor on the fixed
+// variables keep the value they had) — and q carried by the sums above over the slots.  One workgroup; slot c is on thread
+// c mod CG_T in both passes, so no thread reads a word another thread writes.
+__global__ __launch_bounds__(CG_T) void free_image_step_accumulate_kernel(const double* __restrict__ wc, const double* __restrict__ hwc,
+                                                                          const int* __restrict__ map, double* __restrict__ gm, int nfree,
+                                                                          double* __restrict__ sc, int q_mode) {
+    __shared__ double scratch[2 * (CG_T / 64)];
+    if (q_mode != kStepQNone) {
+        double acc[2] = {0.0, 0.0};
+        for (int c = threadIdx.x; c < nfree; c += CG_T) {
+            const int m = map[c];
+            if (m < 0) continue;
+            const double wi = wc[c];
+            acc[0] = fma(wi, gm[m], acc[0]);
+            acc[1] = fma(wi, hwc[c], acc[1]);
+        }
+        block_reduce<CG_T, 2>(acc, scratch, OpSum(), 0.0);
+        if (threadIdx.x == 0) step_q_store(sc, q_mode, acc[0], acc[1]);
     }
-    if (threadIdx.x == 0) out[0] = alpha;
+    for (int c = threadIdx.x; c < nfree; c += CG_T) {
+        const int m = map[c];
+        if (m >= 0) gm[m] = __dadd_rn(gm[m], hwc[c]);
+    }
+}
+
+// The same carry in front of an accumulate on the full vectors (a full-image minor iterate inside a chain whose g_minor is already
+// stale on the fixed variables): the sums run over all n entries, the terms on the fixed variables are +-0 x.  gm is only read.
+__global__ __launch_bounds__(CG_T) void step_carry_q_kernel(const double* __restrict__ w, const double* __restrict__ hw,
+                                                            const double* __restrict__ gm, int n, double* __restrict__ sc) {
+    __shared__ double scratch[2 * (CG_T / 64)];
+    double acc[2] = {0.0, 0.0};
+    for (int i = threadIdx.x; i < n; i += CG_T) {
+        const double wi = w[i];
+        acc[0] = fma(wi, gm[i], acc[0]);
+        acc[1] = fma(wi, hw[i], acc[1]);
+    }
+    block_reduce<CG_T, 2>(acc, scratch, OpSum(), 0.0);
+    if (threadIdx.x == 0) step_q_store(sc, kStepQCarry, acc[0], acc[1]);
 }
 
 }  // namespace bh

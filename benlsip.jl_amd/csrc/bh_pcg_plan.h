@@ -30,7 +30,9 @@ struct PcgSelectIn {
     bool atol_f2b_positive;
     bool allow_free_image;        // false: the compact loop handed this call back
     bool hw_free_part_ok;         // the free part of the accumulated H*w is enough: hw is wanted, option free_image_minor is on and
-                                  // step_from_cg is off (the only consumer left is the line search's w'Hw, and w is zero where fixed)
+                                  // step_from_cg is off (the only consumer left is the line search's w'Hw, and w is zero where fixed),
+                                  // or option free_image_chain is on and step_from_cg is on (bh_step_accumulate_dev takes the free
+                                  // part too: bh_step_chain_plan.h)
 };
 
 struct PcgSelection {

@@ -330,7 +330,10 @@ int32_t bh_linesearch_dev(bh_hess* H, bh_proj* P, const double* g_model_dev, con
 /* r_dev = this rank's d residual rows in HBM (a device-side residual callback); y_bar (q entries) stays a host vector. */
 int32_t bh_grad_dev(bh_hess* H, const double* r_dev, const double* ybar, double* g_out_dev);
 int32_t bh_hmul_add_dev(bh_hess* H, const double* s_dev, const double* g_dev, double* out_n_dev);
-/* s .+= w ; g_minor = H*s + g — src/basic_tralcnlss.jl:436-437 (s_dev is updated in place). */
+/* s .+= w ; g_minor = H*s + g — src/basic_tralcnlss.jl:436-437 (s_dev is updated in place).
+ * Under options "step_from_cg" and "free_image_chain", right behind a bh_minor_iterate_dev that was served from the compact image of
+ * the free columns, g_minor_out_dev holds H*s + g on the FREE variables only afterwards: its entries on the fixed variables keep the
+ * value they had (see "free_image_chain" below). */
 int32_t bh_step_accumulate_dev(bh_hess* H, double* s_dev, const double* w_dev, const double* g_dev, double* g_minor_out_dev);
 /* src/basic_tralcnlss.jl:439-453 on the device-side active set:
  *     active_indx = active_bounds(lincons, x, s, delta)                      src/polyhedral_constraints.jl:219-237 (atol = sqrt(eps))
@@ -496,9 +499,27 @@ int32_t bh_stats_reset(bh_hess* H);
  *                        negative or non-finite alpha leaves alpha * 0 = -0 or NaN there).  After such a call bh_step_accumulate_dev
  *                        always recomputes H*s + g (the fixed part of H*w was never formed), also when "step_from_cg" is switched on
  *                        in between.  A call handed back to the full image (non-finite g on a fixed variable) is today's in every bit.
- *                        With "step_from_cg" = 1 (the resident inner-step chain) the call stays on the full image.  calls_served of
+ *                        With "step_from_cg" = 1 (the resident inner-step chain) the call stays on the full image
+ *                        (unless "free_image_chain" is on).  calls_served of
  *                        bh_hess_free_image_info counts these calls too.  0 = bh_minor_iterate* with "ls_from_cg" = 1 never touches the
  *                        image.  Another value: BH_ERR_INVALID_ARG.
+ *   "free_image_chain" [0] 1 = the same for a bh_minor_iterate* call made with "step_from_cg" = 1 (the resident inner-step chain), by
+ *                        the same rules, policy and hand-back: the line search (free_image_linesearch_scale_hw_kernel) also keeps the
+ *                        FREE part of H*w scaled with w, and the bh_step_accumulate_dev right behind a bh_minor_iterate_dev that was
+ *                        served from the image adds it to g_minor through the slot -> column map
+ *                        (free_image_step_accumulate_kernel): no sweep over J, stats.n_hmul and n_jv unchanged.
+ *                        DEVIATION: after such a call g_minor_out_dev holds H*s + g ON THE FREE VARIABLES ONLY; its entries on the
+ *                        fixed variables keep the value they had.  Nothing inside an inner step reads them (the next CG loop and
+ *                        bh_reduced_gradient_norm_dev mask them; the active set only grows while one J lives).  The model value
+ *                        g.s + s'Hs / 2 cannot be taken from such a g_minor, so it is carried from step to step on the device
+ *                        (q(s + w) = q(s) + w.g_minor + w'Hw / 2 over the free slots, started from the g_minor the library wrote by
+ *                        bh_hmul_add_dev for exactly these H, s, g) and bh_model_reduction_dev returns the carried value without a
+ *                        launch over J; where no value could be carried (g_minor was not the library's own) it takes its J v sweep.
+ *                        A full-image minor iterate inside such a chain (the policy refused a move) keeps today's two vector
+ *                        launches and carries q by one small launch in front of them.  Any other calling pattern (another w, a second
+ *                        accumulate, a bh_pcg* or a minor iterate on any handle in between) recomputes H*s + g over all variables.
+ *                        Independent of "free_image_minor".  0 = every path, launch, counter and bit is what it is without the
+ *                        option.  Another value: BH_ERR_INVALID_ARG.
  *   "gram_ingest"    [0] bh_hess_create_async on one rank with n <= 16384: 1 = the handle is born in the Gram form and G is built during
  *                        the upload, block rows of G as their columns land (see bh_hess_create_async).  Several ranks or n > 16384: the
  *                        call is what it is with 0 (an implicit handle).  Read when the handle is created; no effect on
