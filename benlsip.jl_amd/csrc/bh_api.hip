@@ -169,6 +169,9 @@ struct Ctx {
     // adds it to g_minor on the free variables only and carries the model value q(s) in cg.scalars[kStepQSlot], which
     // bh_model_reduction_dev then returns — no sweep over J anywhere in the chain; 0: such calls stay on the full image
     int64_t opt_free_image_chain = 0;
+    // the three-kernel equality loop (reduced form, mA <= 64, one rank, implicit form, no H*w) on the compact image too, with a
+    // compact image Af of the lineq matrix beside Jf, under the rules of free_image (0 off, 1 on)
+    int64_t opt_free_image_eq = 0;
     // after such a call: cg.hwc, the compact w (cg.s) and H->fi_map (nfree slots) describe the call that delivered w for g_minor = gm
     struct { const void* H = nullptr; const double* w = nullptr; const double* gm = nullptr; int64_t nfree = 0; } hwc_note;
     int64_t opt_gram_ingest = 0;     // bh_hess_create_async, one rank, n <= 16384: the handle is born in the Gram form, G built during the upload
@@ -480,6 +483,9 @@ struct bh_hess {
     std::vector<int32_t> fi_ops_h; // ... as the host planned them (kept until the next call: the upload may still be reading it)
     FreeImageBook fi;              // host record: active set, map, width, credit, counters
     uint64_t fi_epoch = 0;         // bh_proj::mask_epoch of the active set Jf describes (0: none)
+    double* Af = nullptr;          // mA x fi.ldf row-major: the lineq matrix through fi_map (option free_image_eq), zero where the map is -1
+    int64_t Af_doubles = 0;        // capacity of the allocation behind Af
+    uint64_t af_epoch = 0;         // the epoch Af was formed for: it serves iff this is fi_epoch and the caller's mask_epoch (0: none)
     double call_bytes = 0.0;       // bytes of the image the H*p launches of the running bh_pcg stream
     double timed_bytes = 0.0;      // ... summed over the timed_n sampled launches since the last reset or change of form:
     int64_t timed_n = 0;           //     stats.bytes_per_hmul is their mean, the bytes the sampled launches really streamed
@@ -1477,6 +1483,7 @@ int32_t bh_init(int32_t device, int32_t flags) {
     if (const char* s = getenv("BH_CG_FUSED")) g_ctx.opt_cg_fused = std::min<int64_t>(std::max<int64_t>(0, atoll(s)), 2);
     if (const char* s = getenv("BH_FINAL_SYNC")) g_ctx.opt_final_sync = atoll(s) ? 1 : 0;
     if (const char* s = getenv("BH_FREE_IMAGE")) g_ctx.opt_free_image = std::min<int64_t>(std::max<int64_t>(0, atoll(s)), 2);
+    if (const char* s = getenv("BH_FREE_IMAGE_EQ")) g_ctx.opt_free_image_eq = atoll(s) != 0 ? 1 : 0;
     if (const char* s = getenv("BH_CAUCHY_BLOCK")) { if (cauchy_block_value_ok(atoll(s))) g_ctx.opt_cauchy_block = atoll(s); }
     g_ctx.init = true;
     return BH_OK;
@@ -1601,6 +1608,11 @@ int32_t bh_set_option(const char* key, int64_t value) {
     if (!strcmp(key, "free_image_chain")) {
         if (value != 0 && value != 1) return fail(BH_ERR_INVALID_ARG, "free_image_chain is 0 or 1");
         g_ctx.opt_free_image_chain = value;
+        return BH_OK;
+    }
+    if (!strcmp(key, "free_image_eq")) {
+        if (value != 0 && value != 1) return fail(BH_ERR_INVALID_ARG, "free_image_eq is 0 or 1");
+        g_ctx.opt_free_image_eq = value;
         return BH_OK;
     }
     if (!strcmp(key, "gram_ingest")) {
@@ -2176,6 +2188,7 @@ int32_t bh_hess_destroy(bh_hess* H) {
     if (g_ctx.init) (void)hipStreamSynchronize(g_ctx.stream);
     image_release(H->Jd, H->Jd_doubles);
     image_release(H->Jf, H->Jf_doubles);                          // (the stream is drained: no launch still reads the compact image)
+    dev_free(H->Af);
     dev_free(H->fi_map); dev_free(H->fi_ops);
     dev_free(H->vpad); dev_free(H->zpad); dev_free(H->upad); dev_free(H->tbuf); dev_free(H->timg); dev_free(H->timg_gen); dev_free(H->cblk);
     dev_free(H->partials); dev_free(H->sq_partials); dev_free(H->scalar);
@@ -2496,6 +2509,9 @@ static void free_image_release(bh_hess* H) {
         if (g_ctx.init) (void)hipStreamSynchronize(g_ctx.stream);
         image_release(H->Jf, H->Jf_doubles);
     }
+    else if (H->Af && g_ctx.init) (void)hipStreamSynchronize(g_ctx.stream);
+    dev_free(H->Af);                                         // Af goes wherever Jf goes: its slot order is Jf's
+    H->Af = nullptr; H->Af_doubles = 0; H->af_epoch = 0;
     H->Jf = nullptr; H->Jf_doubles = 0; H->fi_epoch = 0;
     H->fi.present = false;
 }
@@ -2578,6 +2594,38 @@ static int32_t free_image_prepare(bh_hess* H, bh_proj* P, bool* use, bool* earns
     return BH_OK;
 }
 
+// Option free_image_eq, behind a free_image_prepare that said "use": Af[r * ldf + c'] = A[r * ldA + map[c']], zero where the map
+// is -1, valid for this call (bh_free_image_plan.h: free_image_af_valid) or formed again by ONE launch enqueued behind the build
+// or the move of Jf, which leaves fi_map current.  It is never moved (at most 64 rows: 2 MiB at n = 4096) and its launch is
+// not priced into the policy.  free_image_build_kernel serves as it stands: it takes source, stride, row count, map,
+// destination and ldf; its grid is min(mA, ...) >= 1 workgroups striding over the rows (row < mA); the 16-byte loads at an even
+// map entry need an even source stride, and the three-kernel shape only exists with ldA == ld, a multiple of 16; the map has ldf
+// entries, every one below n <= ldA or -1; the stores cover [0, ldf) of each of the mA rows of the mA * ldf allocation.
+// *ok = false: the allocation failed — the call stays on the full image without an error.
+static int32_t free_image_prepare_lineq(bh_hess* H, const bh_proj* P, bool* ok) {
+    *ok = false;
+    const FreeImageBook& b = H->fi;
+    if (H->Af != nullptr && free_image_af_valid(H->af_epoch, H->fi_epoch, P->mask_epoch)) { *ok = true; return BH_OK; }
+    const int64_t need = std::max<int64_t>(P->mA, 1) * b.ldf;
+    if (H->Af_doubles < need) {
+        if (H->Af) { (void)hipStreamSynchronize(g_ctx.stream); dev_free(H->Af); }
+        H->Af = nullptr; H->Af_doubles = 0; H->af_epoch = 0;
+        if (hipMalloc(reinterpret_cast<void**>(&H->Af), (size_t)need * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            H->Af = nullptr;
+            return BH_OK;
+        }
+        H->Af_doubles = need;
+    }
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(P->mA, (int64_t)g_ctx.n_cu * 8));
+    hipLaunchKernelGGL(free_image_build_kernel, dim3(grid), dim3(256), 0, g_ctx.stream, (const double*)P->Ad, P->ldA, P->mA, (const int*)H->fi_map,
+                       H->Af, b.ldf);
+    BH_HIP(hipGetLastError());
+    H->af_epoch = H->fi_epoch;
+    *ok = true;
+    return BH_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // projected_cg: the plan of one call (decided once), its run context, one launcher pair per shape
 // ------------------------------------------------------------------------------------------
@@ -2619,11 +2667,11 @@ struct PcgRun {
 };
 
 // Geometry of the fused shape for a loop over `nch` chunks of `n_loop` variables.
-static void pcg_fused_geometry(PcgPlan& p, const bh_hess* H, int nch, int n_loop) {
+static void pcg_fused_geometry(PcgPlan& p, int nch, int n_loop) {
     p.cfg = pick_config(nch);
     p.grid = grid_for(p.cfg, p.nrows);
     p.nblk = (nch + 15) / 16;
-    p.nch_v = p.sel.gen_linv ? H->nchunks : (n_loop + 1) / 2;       // proj_apply_linv_kernel also keeps the padding of v at zero
+    p.nch_v = p.sel.gen_linv ? nch : (n_loop + 1) / 2;              // proj_apply_linv_kernel also keeps the padding of v at zero
     p.nrv = p.sel.fuse_gen ? (p.nch_v + 63) / 64 : p.nblk;
 }
 
@@ -2644,6 +2692,7 @@ static PcgPlan pcg_make_plan(const bh_hess* H, const bh_proj* P, int max_iter, b
     in.rs_cfg_ok = rs_cfg >= 0; in.cgp3_ok = rs_cfg >= 0 && cgp3_supported(rs_cfg); in.peer_blocks_fit = (H->nchunks + 15) / 16 <= kPeerBlkCap;
     in.iterates = max_iter >= 1; in.g_padded = g_padded; in.vectors_in_regs = (n + 1) / 2 <= 4 * CG_T;
     in.hw_wanted = hw_wanted; in.hw_free_part_ok = hw_wanted && hw_free_part_ok; in.atol_f2b_positive = atol_f2b > 0; in.allow_free_image = allow_free_image;
+    in.free_image_eq = g_ctx.opt_free_image_eq;
     p.sel = pcg_select(in);
     const int batch = launch_batch_size(H);
     const bool rccl_path = comm_active() && !use_peer_path();
@@ -2656,7 +2705,7 @@ static PcgPlan pcg_make_plan(const bh_hess* H, const bh_proj* P, int max_iter, b
     p.pbuf[0] = c.p; p.pbuf[1] = c.p2;
     if (p.sel.shape == PCG_FUSED) {
         p.nrows = p.gram ? H->ld : H->d + H->q_eff;                 // Gram form: the rows of the ld x ld image of G
-        pcg_fused_geometry(p, H, H->nchunks, (int)n);
+        pcg_fused_geometry(p, H->nchunks, (int)n);
         p.vv_off = (int)(n_pad / 4);
         p.rvbuf[0] = c.rvpart; p.rvbuf[1] = c.rvpart + n_pad / 2;
         // S(j + 1) speaks for iteration j: either "stopped" (done) or "iter = j + 1, streaming".  Every iteration of the RCCL form
@@ -2686,9 +2735,25 @@ static void pcg_use_free_image(PcgRun& r) {
     if (r.hw != nullptr) r.hw = c.hwc;
     r.on = (int)b.nfree; r.onch = (int)(round_up(b.nfree, 16) / 2);
     r.old = b.ldf;                                            // (after a move the live width is smaller than the stride)
-    pcg_fused_geometry(r.plan, H, r.onch, r.on);
+    pcg_fused_geometry(r.plan, r.onch, r.on);
     H->call_bytes = free_image_bytes(H);
     c.reroute_seq += 1;
+}
+
+// The projection kernels of the three-kernel equality iteration on the compact image (option free_image_eq): A is its compact
+// image Af, mA x ldf; every live slot is free, so there is no mask; W, M, tw and tpart stay the constraint handle's own — they
+// depend on the free set only.  In bounds: proj_left_mul_kernel reads ldf / 2 chunks of a row of Af and of the gathered g
+// (ldf <= ld, the length of every workspace vector; both are zero from nfree on); proj_apply_linv_kernel touches the chunks below
+// nch_pad = round_up(nfree, 16) / 2 <= ldf / 2 of Af and of the vectors, and the (nch_pad + 15) / 16 <= ld / 32 partial blocks
+// of tpart the update kernel wrote.
+// Hand-back (a non-finite g on a fixed variable: the gather raises `reroute`, bh_freeimg.hip.h): the stream and the update
+// kernels of the call return at once, the projection kernels have no such gate and CgState may be a previous call's.  Every
+// launch of a rerouted compact call writes workspace only — the gather: the compact g, w_l, w_u, w (and +0 into the caller's w on
+// the fixed variables, an output the full loop writes in every entry); proj_left_mul_kernel: P->tw; proj_apply_linv_kernel: cg.v,
+// cg.p and the r.v, v.v partials — and the loop on the full image that follows forms all of these again before it reads them
+// (its own init launches; U(1) takes r from g and w = 0).
+static void pcg_compact_proj_args(ProjArgs& pa, const PcgRun& r) {
+    pa.A = r.H->Af; pa.ldA = r.old; pa.n = r.on; pa.nfix = 0; pa.fixrank = nullptr; pa.nch_pad = r.onch;
 }
 
 // ---- fused shape: S(1) | U(1) S(2) | U(2) S(3) | ...  The stream kernel of iteration j+1 is what detects "solved" after
@@ -2750,13 +2815,16 @@ static int32_t pcg_fused_update(PcgRun& r, int j) {
     }
     // (A, L and the vectors are replicated: past the exchange every rank forms the same partials of A_free r, the same v)
     u.A = P->Ad; u.ldA = P->ldA; u.mA = (int)P->mA; u.tpart = P->tpart; u.init_in_memory = p.sel.gen_linv ? 0 : 1;
-    if (p.sel.peer_fused) hipLaunchKernelGGL((cg_reduce_update_kernel<true, true>), dim3(nblk), dim3(256), 0, s, u, g_ctx.peer.args);
+    if (r.fi_use) { u.A = H->Af; u.ldA = r.old; }                 // (u.fixrank is NULL already: every live slot is free)
+    if (r.fi_use) hipLaunchKernelGGL(cg_reduce_update_compact_kernel, dim3(nblk), dim3(256), 0, s, u);
+    else if (p.sel.peer_fused) hipLaunchKernelGGL((cg_reduce_update_kernel<true, true>), dim3(nblk), dim3(256), 0, s, u, g_ctx.peer.args);
     else hipLaunchKernelGGL((cg_reduce_update_kernel<true, false>), dim3(nblk), dim3(256), 0, s, u, PeerArgs{});
     // y = (A_free A_free')^{-1} (A_free r): partial sums + the two triangular solves; then v = r_free - A_free'y and r.v
     ProjArgs pa = proj_args(P, c.d_state, true);
     pa.tpart = P->tpart; pa.tpart_nblk = nblk; pa.rvpart = p.rvbuf[j & 1]; pa.fused_j = j;
     if (p.sel.gen_linv) {
-        pa.W = P->W; pa.nch_pad = H->nchunks; pa.Mgram = p.sel.linv_refine ? P->M : nullptr;
+        pa.W = P->W; pa.nch_pad = r.onch; pa.Mgram = p.sel.linv_refine ? P->M : nullptr;
+        if (r.fi_use) pcg_compact_proj_args(pa, r);
         hipLaunchKernelGGL((proj_apply_linv_kernel<false>), dim3((unsigned)p.nrv), dim3(256), 0, s, pa, (const double*)c.r, c.v);
         return BH_OK;
     }
@@ -2784,11 +2852,13 @@ static int32_t pcg_fused_first(PcgRun& r) {
         }
         // :705-710 in two launches: tw = A_free mask(g); v = P(g), p_1 = -v and the partials of r.v, v.v.  r = g and w = 0 are
         // formed by the first update kernel, CgState is set by workgroup 0 of the first H*p launch (init_done = 2).
+        // (on the compact image: of the gathered g, through Af — r.og is r.a.g otherwise)
         ProjArgs pa = proj_args(P, nullptr, true);
-        hipLaunchKernelGGL(proj_left_mul_kernel, dim3((unsigned)P->mA), dim3(256), 0, s, pa, r.a.g);
+        if (r.fi_use) pcg_compact_proj_args(pa, r);
+        hipLaunchKernelGGL(proj_left_mul_kernel, dim3((unsigned)P->mA), dim3(256), 0, s, pa, r.og);
         pa.tpart = P->tw; pa.tpart_nblk = 1; pa.rvpart = p.rvbuf[0]; pa.vvpart = p.rvbuf[0] + p.vv_off; pa.p_out = c.p;
-        pa.W = P->W; pa.nch_pad = H->nchunks; pa.Mgram = p.sel.linv_refine ? P->M : nullptr; pa.fused_j = 0;
-        hipLaunchKernelGGL((proj_apply_linv_kernel<true>), dim3((unsigned)p.nrv), dim3(256), 0, s, pa, r.a.g, c.v);
+        pa.W = P->W; pa.nch_pad = r.onch; pa.Mgram = p.sel.linv_refine ? P->M : nullptr; pa.fused_j = 0;
+        hipLaunchKernelGGL((proj_apply_linv_kernel<true>), dim3((unsigned)p.nrv), dim3(256), 0, s, pa, r.og, c.v);
     } else if (p.sel.fuse_gen) {
         // :702-718 by the init kernels: r = g, w = 0, v = P(r), rtv, p_1 = -v (in c.p), tol_cg, CgState (stop_at = 0)
         hipLaunchKernelGGL((cg_init_kernel<false>), dim3(1), dim3(CG_T), 0, s, r.a);
@@ -2934,6 +3004,10 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
     if (sel.shape != PCG_SEPARATE || sel.fold_init) BH_TRY(zero_staged_g_padding(c, gp, n, n_pad, g_pad_zeroed));
     bool fi_use = false, fi_earns = false;
     if (sel.free_image_eligible) BH_TRY(free_image_prepare(H, P, &fi_use, &fi_earns));      // (option free_image)
+    if (fi_use && P->mA > 0) {                                                              // (option free_image_eq)
+        BH_TRY(free_image_prepare_lineq(H, P, &fi_use));
+        if (!fi_use) H->fi.served -= 1;
+    }
     if (fi_use) pcg_use_free_image(run);
 
     BH_TRY(pcg_launch_first(run));

@@ -145,6 +145,14 @@ inline void free_image_book_move(FreeImageBook& b, const uint64_t* want, std::ve
     b.moves += k;
 }
 
+// The compact image Af of the lineq matrix A (option "free_image_eq") lives beside Jf and shares its slot order.  It is stamped
+// with the epoch of the constraint handle's active set (library-wide unique: it names the pair of constraint handle and active
+// set).  Af serves a call iff its stamp is the epoch Jf describes and that is the calling constraint handle's; otherwise it is
+// formed again through the current map (at most 2 MiB: never moved).  0 is "none" everywhere.
+inline bool free_image_af_valid(uint64_t af_epoch, uint64_t fi_epoch, uint64_t mask_epoch) {
+    return af_epoch != 0 && af_epoch == fi_epoch && fi_epoch == mask_epoch;
+}
+
 inline int free_image_state(const FreeImageBook& b, const uint64_t* current /* NULL: unknown */) {
     if (!b.present) return FI_STATE_NONE;
     if (current == nullptr) return FI_STATE_VALID;

@@ -33,6 +33,7 @@ struct PcgSelectIn {
                                   // step_from_cg is off (the only consumer left is the line search's w'Hw, and w is zero where fixed),
                                   // or option free_image_chain is on and step_from_cg is on (bh_step_accumulate_dev takes the free
                                   // part too: bh_step_chain_plan.h)
+    int64_t free_image_eq;        // option free_image_eq: the three-kernel equality loop may run on the compact image too
 };
 
 struct PcgSelection {
@@ -82,6 +83,10 @@ inline PcgSelection pcg_select(const PcgSelectIn& in) {
         // the free columns
         o.free_image_eligible = in.allow_free_image && box && !in.gram_handle && !in.comm && (!in.hw_wanted || in.hw_free_part_ok) &&
                                 in.atol_f2b_positive;
+        // Linear equalities (option free_image_eq): the three-kernel shape only, whose operands besides A (W, M, the partials of
+        // A_free r) depend on the free set alone; A gets the same compaction.  No H*w at all here, whatever hw_free_part_ok says.
+        if (in.free_image_eq != 0 && gen_linv && !in.gram_handle && !in.comm && !in.hw_wanted && in.atol_f2b_positive && in.allow_free_image)
+            o.free_image_eligible = true;
         return o;
     }
     // Several ranks over RCCL, box constraints: TWO kernels and the collective per iteration — the update of iteration j-1 moves

@@ -519,7 +519,9 @@ def set_option(key, value):
     default 0) and ``free_image_minor`` (``minor_iterate`` with ``ls_from_cg`` = 1 and ``step_from_cg`` = 0 may run its CG loop and its
     line search on the compact image of the free columns under the rules of ``free_image``, default 0) and ``free_image_chain`` (the same
     for the resident chain of ``inner_step``, which runs with ``step_from_cg`` = 1: ``bh_step_accumulate_dev`` then keeps ``g_minor`` up on
-    the free variables only and the model value is carried from step to step, default 0)."""
+    the free variables only and the model value is carried from step to step, default 0) and ``free_image_eq`` (``projected_cg`` with
+    up to 64 linear equalities in the three-kernel iteration on one rank may run on the compact image too, with a compact image of ``A``
+    beside it, under the rules of ``free_image``, default 0)."""
     check(_lib.lib().bh_set_option(key.encode(), int(value)), "bh_set_option(%s)" % key)
 
 

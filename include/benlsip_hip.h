@@ -520,6 +520,20 @@ int32_t bh_stats_reset(bh_hess* H);
  *                        accumulate, a bh_pcg* or a minor iterate on any handle in between) recomputes H*s + g over all variables.
  *                        Independent of "free_image_minor".  0 = every path, launch, counter and bit is what it is without the
  *                        option.  Another value: BH_ERR_INVALID_ARG.
+ *   "free_image_eq"  [0] 1 = a bh_pcg* call with linear equalities is considered for the compact image by the rules and the policy of
+ *                        "free_image" (0 off, 1 by the policy, 2 always) when it takes the three-kernel iteration ("cg_fused" = 1, the
+ *                        reduced projection form, mA <= 64) on one rank in the implicit form with atol_f2b > 0 and no H*w wanted.  The
+ *                        handle then also keeps Af, the mA x ldf image of the lineq matrix in the slot order of the compact image,
+ *                        formed again by one launch whenever the constraint handle or its active set is another than the one it was
+ *                        formed for (never moved; its launch is not part of the policy's costs).  The loop is the one of the full
+ *                        image on compact operands: in every bit the call a fresh pair of handles makes on the columns of the free
+ *                        variables in slot order, nothing fixed.  w is exactly 0 on the fixed variables.  A non-finite g on a fixed
+ *                        variable: the call runs on the full image.  bh_minor_iterate* with an H*w buffer, "cg_fused" = 2, the
+ *                        seven-kernel shape, mA > 64, the augmented form, the Gram form and several ranks stay on the full image.
+ *                        stats.bytes_per_hmul, bh_time_kernel kind 0 and bh_hess_free_image_info report these calls as they report
+ *                        box-constrained ones.  0 = every path, launch, counter and bit is what it is without the option.
+ *                        Another value: BH_ERR_INVALID_ARG.  (The environment variable BH_FREE_IMAGE_EQ, read by bh_init, sets
+ *                        the initial value.)
  *   "gram_ingest"    [0] bh_hess_create_async on one rank with n <= 16384: 1 = the handle is born in the Gram form and G is built during
  *                        the upload, block rows of G as their columns land (see bh_hess_create_async).  Several ranks or n > 16384: the
  *                        call is what it is with 0 (an implicit handle).  Read when the handle is created; no effect on
