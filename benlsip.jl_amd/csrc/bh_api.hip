@@ -149,12 +149,9 @@ struct Ctx {
     // Opt-in: it relies on the CALLER'S invariant that g_minor_out holds H*s + g for the current s (true in inner_step,
     // src/basic_tralcnlss.jl:412,:434-437; the library's resident inner-step mirrors switch it on around their loop)
     int64_t opt_step_from_cg = 0;
-    struct { const void* H = nullptr; const double* w = nullptr; const double* gm = nullptr; } hw_note;   // what cg.hw currently is H*w of
-    // the last (H, s, g, g_minor) for which the library itself wrote g_minor = H*s + g (bh_hmul_add_dev, bh_step_accumulate_dev):
-    // with step_from_cg on, bh_model_reduction_dev on the same H, s, g takes s'Hs = s.(g_minor - g) instead of sweeping J
-    // fixed_part_stale, q_valid: the chain of steps behind option free_image_chain (bh_step_chain_plan.h)
-    struct { const void* H = nullptr; const double* s = nullptr; const double* g = nullptr; const double* gm = nullptr;
-             bool fixed_part_stale = false, q_valid = false; } gm_note;
+    // what cg.hw, cg.hwc and the caller's g_minor currently are products of, for the two options above and free_image_chain below:
+    // written and read only through the events of bh_step_chain_plan.h
+    StepNotes notes;
     int64_t opt_fold_init = 1;       // box CG: fold the initialisation into the first H*p / step launches
     int64_t opt_final_sync = 0;      // *_dev: always drain the stream before returning (1), or only wait for what the host is owed (0)
     int64_t opt_host_copy_kernels = 1;   // host vectors of the host-pointer entry points: copy kernels on the mapped pinned arena (1) or DMA (0)
@@ -172,8 +169,6 @@ struct Ctx {
     // the three-kernel equality loop (reduced form, mA <= 64, one rank, implicit form, no H*w) on the compact image too, with a
     // compact image Af of the lineq matrix beside Jf, under the rules of free_image (0 off, 1 on)
     int64_t opt_free_image_eq = 0;
-    // after such a call: cg.hwc, the compact w (cg.s) and H->fi_map (nfree slots) describe the call that delivered w for g_minor = gm
-    struct { const void* H = nullptr; const double* w = nullptr; const double* gm = nullptr; int64_t nfree = 0; } hwc_note;
     int64_t opt_gram_ingest = 0;     // bh_hess_create_async, one rank, n <= 16384: the handle is born in the Gram form, G built during the upload
     int64_t opt_ev_stride = 8;       // BH_FLAG_PROFILE: hipEvents around every opt_ev_stride-th H*p launch of a handle
     // RCCL
@@ -533,9 +528,7 @@ int32_t ensure_cg_workspace(int64_t n_pad, int64_t trace_cap) {
         constexpr int NV = 20;
         dev_free(c.slab);
         c.slab = nullptr;
-        g_ctx.hw_note = {};                      // cg.hw and cg.hwc go with the old slab ...
-        g_ctx.hwc_note = {};
-        g_ctx.gm_note.q_valid = false;           // ... and so does the carried q (cg.scalars)
+        g_ctx.notes.workspace_gone();
         BH_TRY(dev_alloc(&c.slab, NV * n_pad + 8));
         BH_HIP(hipMemsetAsync(c.slab, 0, (size_t)(NV * n_pad + 8) * sizeof(double), g_ctx.stream));
         for (int i = 0; i < NV; ++i) *vecs[i] = c.slab + (int64_t)i * n_pad;
@@ -1501,8 +1494,7 @@ int32_t bh_shutdown(void) {
     dev_free(c.slab); dev_free(c.d_state); dev_free(c.d_trace); dev_free(c.d_reroute);
     if (c.h_mirror) (void)hipHostFree(const_cast<unsigned long long*>(c.h_mirror));
     c = CgWorkspace();
-    g_ctx.hwc_note = {};
-    g_ctx.gm_note.q_valid = false;
+    g_ctx.notes.workspace_gone();
     dev_free(g_ctx.scratch_dev); g_ctx.scratch_dev = nullptr;
     dev_free(g_ctx.rbuf); g_ctx.rbuf = nullptr; g_ctx.rbuf_cap = 0;
     if (g_ctx.mbox_h) { (void)hipHostFree(const_cast<unsigned long long*>(g_ctx.mbox_h)); g_ctx.mbox_h = nullptr; g_ctx.mbox_d = nullptr; }
@@ -2067,8 +2059,7 @@ int32_t bh_hess_set_mu(bh_hess* H, double mu) {
     if (mu == H->mu) return BH_OK;          // the Julia shim calls this on every handle(H): never a rebuild
     H->mu = mu;
     H->G_valid = false;                      // Gram form: rebuilt before the next product that reads G
-    if (g_ctx.hwc_note.H == H) g_ctx.hwc_note = {};                        // cg.hwc is H*w of the old mu ...
-    if (g_ctx.gm_note.H == H) g_ctx.gm_note.q_valid = false;               // ... and the carried q its model value
+    g_ctx.notes.handle_changed(H);
     return BH_OK;
 }
 
@@ -2095,9 +2086,7 @@ static int32_t gram_enter(bh_hess* H) {
     H->form = BH_HESS_GRAM;
     H->stats.bytes_per_hmul = hmul_bytes(H);
     H->timed_bytes = 0.0; H->timed_n = 0;
-    if (g_ctx.hw_note.H == H) g_ctx.hw_note = {};
-    if (g_ctx.hwc_note.H == H) g_ctx.hwc_note = {};
-    if (g_ctx.gm_note.H == H) g_ctx.gm_note = {};
+    g_ctx.notes.handle_changed(H);
     return BH_OK;
 }
 
@@ -2117,9 +2106,7 @@ int32_t bh_hess_set_form(bh_hess* H, int32_t form) {
     H->form = form;
     H->stats.bytes_per_hmul = hmul_bytes(H);
     H->timed_bytes = 0.0; H->timed_n = 0;
-    if (g_ctx.hw_note.H == H) g_ctx.hw_note = {};
-    if (g_ctx.hwc_note.H == H) g_ctx.hwc_note = {};
-    if (g_ctx.gm_note.H == H) g_ctx.gm_note = {};
+    g_ctx.notes.handle_changed(H);
     return rc;
 }
 
@@ -2174,9 +2161,7 @@ int32_t bh_hess_free_image_read(bh_hess* H, double* image_out, int64_t image_cap
 }
 
 int32_t bh_hess_destroy(bh_hess* H) {
-    if (H && g_ctx.hw_note.H == H) g_ctx.hw_note = {};
-    if (H && g_ctx.hwc_note.H == H) g_ctx.hwc_note = {};
-    if (H && g_ctx.gm_note.H == H) g_ctx.gm_note = {};
+    g_ctx.notes.handle_changed(H);
     if (!H) return BH_OK;
     if (H->up) {                              // an upload still in flight: let it finish before its buffers go
         AsyncUpload* u = H->up;
@@ -2504,7 +2489,7 @@ static int launch_batch_size(const bh_hess* H) {
 // ---- compact image of the free columns (option free_image) ----------------------------------
 // Jf goes back to the image pool.  (Launches that read it may be queued: the stream is drained first.)
 static void free_image_release(bh_hess* H) {
-    if (g_ctx.hwc_note.H == H) g_ctx.hwc_note = {};          // the map goes with the image
+    g_ctx.notes.compact_slots_changed(H);                    // the map goes with the image
     if (H->Jf) {
         if (g_ctx.init) (void)hipStreamSynchronize(g_ctx.stream);
         image_release(H->Jf, H->Jf_doubles);
@@ -2548,7 +2533,7 @@ static int32_t free_image_prepare(bh_hess* H, bh_proj* P, bool* use, bool* earns
     }
     if (act == FI_USE) { H->fi_epoch = P->mask_epoch; b.served += 1; *use = true; return BH_OK; }        // an identical mask pushed again
     if (act == FI_MOVE) {
-        if (g_ctx.hwc_note.H == H) g_ctx.hwc_note = {};      // the slots change hands
+        g_ctx.notes.compact_slots_changed(H);
         free_image_book_move(b, want, H->fi_ops_h);
         const int k = (int)H->fi_ops_h.size();
         count_h2d((size_t)k * sizeof(int));
@@ -2571,7 +2556,7 @@ static int32_t free_image_prepare(bh_hess* H, bh_proj* P, bool* use, bool* earns
             return BH_OK;
         }
     }
-    if (g_ctx.hwc_note.H == H) g_ctx.hwc_note = {};
+    g_ctx.notes.compact_slots_changed(H);
     free_image_book_build(b, want, n);
     b.present = false;                                       // until the image exists
     const int64_t need = std::max<int64_t>(nrows, 1) * b.ldf;
@@ -2979,8 +2964,7 @@ static int32_t pcg_run(bh_hess* H, bh_proj* P, const double* gp, const double* w
     if (max_iter64 >= 0xfffff) return fail(BH_ERR_UNSUPPORTED, "2*(n - mA - count(fixvars)) exceeds the 20-bit iteration counters of the progress word");
     CgWorkspace& c = g_ctx.cg;
     H->ev_pending.clear();
-    if (hw != nullptr) g_ctx.hw_note = {};          // cg.hw is about to be overwritten
-    g_ctx.hwc_note = {};                            // any loop may run on the compact image: its gather rewrites the compact operands
+    g_ctx.notes.cg_loop_begins(hw != nullptr);
     H->call_bytes = hmul_bytes(H);
 
     PcgRun run{H, P, c, g_ctx.stream};
@@ -3241,7 +3225,7 @@ static int32_t minor_iterate_impl(bh_hess* H, bh_proj* P, const double* x, const
     // instead of another sweep over J (-0.3 ms per minor iterate at config 3); mathematically identical, rounding ~1e-15.
     double* hw = g_ctx.opt_ls_from_cg ? c.hw : nullptr;
     if (!dev) {
-        g_ctx.hwc_note = {};                                                         // (the compact operands live in these vectors)
+        g_ctx.notes.compact_operands_overwritten();
         BH_TRY(stage_vecs(c.s, {s_vec, x, xlow, xupp, g_model}, n, c.n_pad));      // c.s, c.x, c.xlow, c.xupp, c.g are consecutive
         xp = c.x; sp = c.s; lop = c.xlow; upp = c.xupp;
         BH_TRY(mbox_ensure());
@@ -3292,11 +3276,9 @@ static int32_t minor_iterate_impl(bh_hess* H, bh_proj* P, const double* x, const
         BH_TRY(finish_device_call());
     }
     BH_TRY(pcg_finish(H, fin, !dev));
-    // cg.hw now holds H*w for the w just delivered (scaled with it by the line search): bh_step_accumulate_dev may use it.
-    // Not after a loop on the compact image: that one left the free part of H*w in cg.hwc and cg.hw as it was.
-    if (dev && hw != nullptr && !fin.compact) { g_ctx.hw_note.H = H; g_ctx.hw_note.w = w_out; g_ctx.hw_note.gm = g_model; }
-    // In the chain cg.hwc is that H*w on the free variables, in slot order beside the compact w (cg.s) and the handle's map.
-    if (dev && hw != nullptr && fin.compact && chain) g_ctx.hwc_note = {H, w_out, g_model, H->fi.nfree};
+    // cg.hw (or, after a loop on the compact image in the chain, cg.hwc) now holds H*w for the w just delivered, scaled with it by
+    // the line search: bh_step_accumulate_dev may use it
+    g_ctx.notes.minor_iterate_done(H, w_out, g_model, dev, hw != nullptr, fin.compact, chain, H->fi.nfree);
     if (status) *status = fin.status;
     if (iters) *iters = fin.iter;
     if (n_hmul_out) *n_hmul_out = fin.n_hmul;
@@ -3380,7 +3362,7 @@ static int32_t hmul_add_impl(bh_hess* H, const double* s_vec, const double* g, d
     }
     BH_TRY(dev ? finish_device_call() : sync_flush());
     H->stats.n_hmul += 1;
-    if (dev) g_ctx.gm_note = {H, s_vec, g, out_n}; else g_ctx.gm_note = {};
+    g_ctx.notes.gminor_written(H, s_vec, g, out_n, dev);
     return BH_OK;
 }
 int32_t bh_hmul_add(bh_hess* H, const double* s_vec, const double* g, double* out_n) { return hmul_add_impl(H, s_vec, g, out_n, false); }
@@ -3402,16 +3384,10 @@ int32_t bh_step_accumulate_dev(bh_hess* H, double* s_dev, const double* w_dev, c
     // q(s + w) = q(s) + w.g_minor + w'Hw / 2 over the free slots.  Which path runs: step_acc_select (bh_step_chain_plan.h).
     const bool ok = g_ctx.init && H && g_dev && g_minor_out_dev;
     CgWorkspace& c = g_ctx.cg;
-    StepAccIn in{};
+    const bool compact_live = ok && c.hwc != nullptr && H->fi.present && H->fi_map != nullptr;
+    StepAccIn in = g_ctx.notes.accumulate_begins(H, w_dev, g_minor_out_dev, s_dev, g_dev, ok, c.hw != nullptr, compact_live, ok ? H->fi.nfree : 0);
     in.step_from_cg = g_ctx.opt_step_from_cg; in.free_image_chain = g_ctx.opt_free_image_chain;
-    in.full_note = ok && g_ctx.hw_note.H == H && g_ctx.hw_note.w == w_dev && g_ctx.hw_note.gm == g_minor_out_dev && c.hw != nullptr;
-    in.compact_note = ok && g_ctx.hwc_note.H == H && g_ctx.hwc_note.w == w_dev && g_ctx.hwc_note.gm == g_minor_out_dev && c.hwc != nullptr &&
-                      H->fi.present && H->fi_map != nullptr && H->fi.nfree == g_ctx.hwc_note.nfree;
-    in.gm_note_match = ok && g_ctx.gm_note.H == H && g_ctx.gm_note.s == s_dev && g_ctx.gm_note.g == g_dev && g_ctx.gm_note.gm == g_minor_out_dev;
-    in.fixed_part_stale = g_ctx.gm_note.fixed_part_stale; in.q_valid = g_ctx.gm_note.q_valid;
     const StepAccPlan plan = step_acc_select(in);
-    g_ctx.hw_note = {};                              // one use: s changes below, a second call with the same w is a different step
-    g_ctx.hwc_note = {};
     if (plan.path == STEP_ACC_SWEEP) return hmul_add_impl(H, s_dev, g_dev, g_minor_out_dev, true, w_dev, s_dev);
     const int64_t n = H->n;
     const int grid = std::max(1, std::min((int)((n + 255) / 256), 1024));
@@ -3433,7 +3409,7 @@ int32_t bh_step_accumulate_dev(bh_hess* H, double* s_dev, const double* w_dev, c
                            (const int*)H->fi_map, g_minor_out_dev, (int)H->fi.nfree, c.scalars, q_mode);
     }
     BH_HIP(hipGetLastError());
-    g_ctx.gm_note = {H, s_dev, g_dev, g_minor_out_dev, plan.fixed_part_stale, plan.q_valid};
+    g_ctx.notes.accumulate_done(H, s_dev, g_dev, g_minor_out_dev, plan);
     return finish_device_call();
 }
 
@@ -3528,8 +3504,8 @@ int32_t bh_model_reduction_dev(bh_hess* H, const double* g_dev, const double* s_
     if (!H || !g_dev || !s_dev || !out) return fail(BH_ERR_INVALID_ARG, "NULL argument");
     BH_TRY(ensure_cg_workspace(H->ld, 0));
     CgWorkspace& c = g_ctx.cg;
-    const bool note = g_ctx.gm_note.H == H && g_ctx.gm_note.s == s_dev && g_ctx.gm_note.g == g_dev && g_ctx.gm_note.gm != nullptr;
-    const ModelPath path = model_select(g_ctx.opt_step_from_cg, note, g_ctx.gm_note.fixed_part_stale, g_ctx.gm_note.q_valid);
+    const ModelQuery note = g_ctx.notes.model_query(H, s_dev, g_dev);
+    const ModelPath path = model_select(g_ctx.opt_step_from_cg, note.match, note.fixed_part_stale, note.q_valid);
     if (path == MODEL_CARRIED) {
         // a chain of steps under option free_image_chain: g_minor is stale on the fixed variables, q(s) was carried instead
         // (bh_step_accumulate_dev) — it rides to the host with the seal, no launch of its own
@@ -3541,7 +3517,7 @@ int32_t bh_model_reduction_dev(bh_hess* H, const double* g_dev, const double* s_
     if (path == MODEL_FROM_GMINOR) {
         // the library wrote g_minor = H*s + g for exactly these vectors (and, by the caller's opt-in, nobody has touched them since):
         // s'Hs = s.(g_minor - g), g.s — no sweep over J (the rounding of the difference is that of g.s itself: eps |g||s|)
-        hipLaunchKernelGGL(model_from_gminor_kernel, dim3(1), dim3(CG_T), 0, g_ctx.stream, g_dev, s_dev, g_ctx.gm_note.gm, (int)H->n, c.scalars + 2);
+        hipLaunchKernelGGL(model_from_gminor_kernel, dim3(1), dim3(CG_T), 0, g_ctx.stream, g_dev, s_dev, static_cast<const double*>(note.gm), (int)H->n, c.scalars + 2);
         BH_HIP(hipGetLastError());
         BH_TRY(mbox_ensure());
         BH_TRY(mbox_seal_and_wait(2 * sizeof(double), c.scalars + 2, c.scalars + 3, mbox_dev<double>(kMbScal)));
@@ -4017,7 +3993,7 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
         BH_TRY(ensure_trsv_lds(lds));
     }
     // (the Cauchy kernels read x, g and the bounds element by element: a device caller's vectors are used where they lie)
-    if (!dev) g_ctx.hwc_note = {};                                                  // (the compact operands of a minor iterate live in these vectors)
+    if (!dev) g_ctx.notes.compact_operands_overwritten();
     if (!dev) BH_TRY(stage_vecs(c.x, {x, xlow, xupp, g}, n, c.n_pad));            // c.x, c.xlow, c.xupp, c.g are consecutive
 
     CauchyRun run{H, P, c, s};

@@ -404,6 +404,8 @@ int32_t bh_stats_reset(bh_hess* H);
  *                        Under the same option bh_model_reduction_dev(H, g, s) takes s'Hs = s.(g_minor - g) from the g_minor the
  *                        library last wrote for exactly these H, s, g (bh_hmul_add_dev / bh_step_accumulate_dev) instead of a J v sweep.
  *                        0, or any other calling pattern: the explicit product.  Needs "ls_from_cg" = 1.
+ *                        After a bh_hess_set_mu that changes mu, the next bh_step_accumulate_dev and bh_model_reduction_dev on that
+ *                        handle recompute from J.
  *   "chol_downdate"  [0] bh_cauchy_step, per breakpoint: 0 = downdate the Gram matrix and refactor (as accurate as the reference's
  *                        from-scratch rebuild), 1 = for mA > 64 only: rank-one downdate of the factor itself (O(mA^2)), rebuilt from
  *                        scratch every 8th breakpoint (errors accumulate in between; up to 64 rows the refactoring path is as fast)

@@ -470,23 +470,25 @@ def test_a_zero_curvature_iterate_in_the_chain_leaves_w_unscaled(bh, n_cu):
 
 
 # ------------------------------------------------------------------------------------------------------------------ 8. hygiene
-@pytest.mark.parametrize("disturbance", ["pcg", "other_handle", "other_w", "second_accumulate"])
-def test_anything_between_the_minor_iterate_and_the_accumulate_sends_it_down_the_sweep(bh, n_cu, disturbance):
+def _disturbed_accumulate(bh, n_cu, disturbance, compact):
+    """compact: the chain under test runs on the compact image (free_image_chain = 1) against the compact step_from_cg = 0 chain
+    (free_image_minor = 1); otherwise both run on the full image (free_image_chain = 0, free_image_minor = 0)."""
     I = F.instance("S3", n_cu)                                      # n == ld: bh_pcg_dev takes device vectors in place
     st = F.states("S3")[0]
     n, g, Ho = I["n"], I["g"], I["Ho"]
     s0 = 0.01 * np.random.default_rng(41).standard_normal(n)
     steps = 2 if disturbance == "second_accumulate" else 1
     out = {}
-    for key, (chain, sfc) in (("reference", (0, 0)), ("disturbed", (1, 1))):      # reference: the step_from_cg = 0 chain, compact too
+    # reference: the step_from_cg = 0 chain on the same image
+    for key, (chain, minor, sfc) in (("reference", (0, int(compact), 0)), ("disturbed", (int(compact), 0, 1))):
         H = bh.AlHessian(I["J"], I["C"], F.MU)
         P = _constraints(bh, n, st.fix.copy())
         ch = Chain(bh, H, n, s0, g)
         extra = []
         try:
-            _mode(bh, chain=chain, minor=1 - chain, sfc=sfc)
+            _mode(bh, chain=chain, minor=minor, sfc=sfc)
             got = ch.minor(P)
-            assert H.free_image_info(None)["calls_served"] == 1
+            assert H.free_image_info(None)["calls_served"] == int(compact)
             w_arg = None
             if key == "disturbed" and disturbance == "pcg":
                 big = 1e6 * np.ones(n)
@@ -506,6 +508,9 @@ def test_anything_between_the_minor_iterate_and_the_accumulate_sends_it_down_the
             elif key == "disturbed" and disturbance == "other_w":
                 extra = [bh.DeviceVector(n, got[0])]
                 w_arg = extra[0]
+            elif key == "disturbed" and disturbance == "set_mu":
+                H.mu = 2 * F.MU                                     # cg.hw, cg.hwc, g_minor and the carried q are of another operator now ...
+                H.mu = F.MU                                         # ... and the library does not look whether it comes back
             sweeps = [ch.accumulate(w_arg) for _ in range(steps)]
             if key == "reference":
                 assert sweeps == [(1, 0)] * steps
@@ -528,3 +533,33 @@ def test_anything_between_the_minor_iterate_and_the_accumulate_sends_it_down_the
     _same_call(out["disturbed"][0], out["reference"][0], disturbance)
     assert np.array_equal(_bits(out["disturbed"][1]), _bits(out["reference"][1])), (disturbance, "s")
     assert np.array_equal(_bits(out["disturbed"][2]), _bits(out["reference"][2])), (disturbance, "g_minor")
+
+
+@pytest.mark.parametrize("disturbance", ["pcg", "other_handle", "other_w", "second_accumulate", "set_mu"])
+def test_anything_between_the_minor_iterate_and_the_accumulate_sends_it_down_the_sweep(bh, n_cu, disturbance):
+    _disturbed_accumulate(bh, n_cu, disturbance, compact=True)
+
+
+def test_a_changed_mu_sends_the_full_image_chain_down_the_sweep_too(bh, n_cu):
+    """free_image_chain = 0, free_image_minor = 0, step_from_cg = 1: cg.hw is H*w of the old mu as much as cg.hwc is.  (A library that
+    clears the compact note alone takes the two vector launches here: [(0, 0)].)"""
+    _disturbed_accumulate(bh, n_cu, "set_mu", compact=False)
+
+
+def test_a_changed_mu_sends_the_model_value_back_to_the_sweep(bh, n_cu):
+    """bh_hmul_add_dev notes g_minor = H*s + g; with another mu that g_minor is no longer of this H, and s.(g_minor - g) no longer s'Hs."""
+    I = F.instance("S3", n_cu)
+    n, g = I["n"], I["g"]
+    s0 = 0.01 * np.random.default_rng(43).standard_normal(n)
+    H = bh.AlHessian(I["J"], I["C"], F.MU)
+    ch = Chain(bh, H, n, s0, g)                                     # (bh_hmul_add_dev(H, s, g, gm))
+    try:
+        _mode(bh, chain=0, minor=0, sfc=1)
+        H.mu = 2 * F.MU
+        value, d_jv = ch.model()
+        assert d_jv == 1
+        _assert_model(value, g, s0, R.AlHessian(I["J"], I["C"], 2 * F.MU), "model value after set_mu(2 mu)")
+    finally:
+        _restore(bh)
+        ch.close()
+        H.close()
