@@ -7,6 +7,7 @@
 #include "bh_gram_ingest_plan.h"
 #include "bh_kernels.hip.h"
 #include "bh_launch_ahead.h"
+#include "bh_options.h"
 #include "bh_pcg_plan.h"
 #include "bh_step_chain_plan.h"
 
@@ -112,7 +113,7 @@ struct AsyncUpload {
     bool resources() const { return s_copy != nullptr; }
 };
 
-struct Ctx {
+struct Ctx : Options {   // the opt_* fields of bh_set_option: bh_options.h
     bool init = false;
     int device = -1;
     int flags = 0;
@@ -120,57 +121,9 @@ struct Ctx {
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     std::string detail;
-    // options
-    int64_t opt_blocks_per_cu = 0;   // 0 = per-config default
-    int64_t opt_batch = 0;           // CG iterations launched ahead of the host's done-flag poll; 0 = by problem size (auto_batch)
-    // Cauchy search, per breakpoint: 0 = downdate the Gram matrix A_free A_free' and refactor it (O(mA^3), the default: its
-    // factor is as accurate as the reference's from-scratch rebuild), 1 = for mA > 64: rank-one downdate of the factor itself
-    // (O(mA^2)), refreshed from scratch every kDowndateRefresh breakpoints.  Errors accumulate over the downdates — measured on the
-    // 48-parameter NLS (mA = 2, when the one-wave kernel for mA <= 64 still existed): after 29 of them a search direction P(-g)
-    // with ||g||/||P(-g)|| = 1.7e7 took one more breakpoint than the oracle; after 40, with A_free A_free' close to singular, the
-    // projections had left null(A).  Up to 64 rows the refactoring path costs the same, so it is the only one there.
-    int64_t opt_chol_downdate = 0;
-    // bh_cauchy_step with box constraints on one rank: 1 = image-space search (J d and J s_c maintained by rank-one column updates:
-    // one J v sweep at the start, then no sweep over J per breakpoint), 0 = one H*d sweep per breakpoint as the reference does
-    int64_t opt_cauchy_image = 1;
-    int64_t opt_cauchy_image_max_ma = 64;   // ... and with up to this many linear equalities (0..64)
-    int64_t opt_cauchy_image_refresh = 0;   // row-space search, one rank: R >= 1 forms t_d, t_s (a, B, t_s) again from J every R-th pass (0: never)
-    int64_t opt_cauchy_fused = 1;           // box constraints, one rank, row-space form: ONE kernel per breakpoint (cauchy_fused_kernel)
-    int64_t opt_cauchy_block = 0;           // ... and K = 2, 4, 8 or 16 breakpoints per launch of it (cauchy_block_kernel<K>; 0, 1: one)
-    int64_t opt_cauchy_gram_eq = 0;         // Gram-form handle, 1 <= mA <= 64, one rank: the search with linear equalities from G (cauchy_gram_eq_kernel)
-    int64_t opt_cauchy_gram = 0;            // Gram-form handle, box constraints, one rank: the whole search from G in one launch (cauchy_gram_kernel)
-    int64_t opt_linv_refine = 1;            // explicit-inverse projection (three-kernel CG iteration): one step of iterative refinement of y
-    int64_t opt_cauchy_gemm = 1;            // B = J D A' of that form in one sweep on the matrix cores (0: mA J v sweeps over masked rows of A)
-    int64_t opt_gram_cg_fused = 0;          // Gram-form handle: fused CG iteration (gram_cg_kernel + update: two kernels; <= 64 equalities: three)
-    int64_t opt_gram_mfma = 1;       // A_free A_free': 1 = matrix cores when mA > 96, 2 = always, 0 = never (one wave per entry, VALU)
-    int64_t opt_ls_from_cg = 1;      // minor_iterate: linesearch's w'Hw from the H*w accumulated by the CG loop
-    // bh_step_accumulate_dev right behind the bh_minor_iterate_dev that produced its w: g_minor += H*w with the H*w that CG loop
-    // accumulated (scaled with w by the line search) instead of a fresh sweep H*s + g over J — one H-product less per minor iterate.
-    // Opt-in: it relies on the CALLER'S invariant that g_minor_out holds H*s + g for the current s (true in inner_step,
-    // src/basic_tralcnlss.jl:412,:434-437; the library's resident inner-step mirrors switch it on around their loop)
-    int64_t opt_step_from_cg = 0;
-    // what cg.hw, cg.hwc and the caller's g_minor currently are products of, for the two options above and free_image_chain below:
+    // what cg.hw, cg.hwc and the caller's g_minor currently are products of, for the options ls_from_cg, step_from_cg and free_image_chain:
     // written and read only through the events of bh_step_chain_plan.h
     StepNotes notes;
-    int64_t opt_fold_init = 1;       // box CG: fold the initialisation into the first H*p / step launches
-    int64_t opt_final_sync = 0;      // *_dev: always drain the stream before returning (1), or only wait for what the host is owed (0)
-    int64_t opt_host_copy_kernels = 1;   // host vectors of the host-pointer entry points: copy kernels on the mapped pinned arena (1) or DMA (0)
-    int64_t opt_cg_fused = 1;        // box CG: two kernels per iteration (H*p with the p-update folded in + reduce/update) instead of three
-    int64_t opt_proj_form = 1;       // 1: reduced mA x mA form (fast), 0: the reference's augmented mpp x mpp form
-    int64_t opt_upload_chunk_mb = 64; // bh_hess_create_async: MiB of J per pipelined column chunk
-    int64_t opt_free_image = 1;      // box CG loop, one rank: stream the compact image of the free columns (0 off, 1 by the policy of bh_free_image_plan.h, 2 always)
-    // bh_minor_iterate* with ls_from_cg = 1 and step_from_cg = 0: the call is considered for the compact image like a bh_pcg* (the
-    // loop accumulates the free part of H*w, free_image_linesearch_kernel takes the line search on the compact operands); 0: never
-    int64_t opt_free_image_minor = 0;
-    // the same with step_from_cg = 1, the resident inner-step chain: the line search keeps cg.hwc scaled with w, bh_step_accumulate_dev
-    // adds it to g_minor on the free variables only and carries the model value q(s) in cg.scalars[kStepQSlot], which
-    // bh_model_reduction_dev then returns — no sweep over J anywhere in the chain; 0: such calls stay on the full image
-    int64_t opt_free_image_chain = 0;
-    // the three-kernel equality loop (reduced form, mA <= 64, one rank, implicit form, no H*w) on the compact image too, with a
-    // compact image Af of the lineq matrix beside Jf, under the rules of free_image (0 off, 1 on)
-    int64_t opt_free_image_eq = 0;
-    int64_t opt_gram_ingest = 0;     // bh_hess_create_async, one rank, n <= 16384: the handle is born in the Gram form, G built during the upload
-    int64_t opt_ev_stride = 8;       // BH_FLAG_PROFILE: hipEvents around every opt_ev_stride-th H*p launch of a handle
     // RCCL
     void* rccl_lib = nullptr;
     ncclComm_t comm = nullptr;
@@ -190,7 +143,6 @@ struct Ctx {
     // driver scrub the memory in the background (-5 % HBM bandwidth for ~60 ms) and the next hipMalloc costs ~4 ms
     struct PooledImage { double* ptr; int64_t doubles; };
     std::vector<PooledImage> image_pool;
-    int64_t opt_image_pool = 2;      // images kept (0: free at once)
     int64_t image_pool_hits = 0;
     AsyncUpload* upload_cache = nullptr;   // streams, events and staging buffers of the last finished asynchronous upload, kept for the next
     // host <-> device traffic issued by the library since bh_init (bh_stats: the device-resident entry points are checked against it)
@@ -1469,15 +1421,7 @@ int32_t bh_init(int32_t device, int32_t flags) {
     g_ctx.stream = g_ctx.own_stream;
     BH_TRY(dev_alloc(&g_ctx.scratch_dev, 1024));
     BH_TRY(mbox_ensure());
-    if (const char* s = getenv("BH_HOST_COPY_KERNELS")) g_ctx.opt_host_copy_kernels = atoll(s) ? 1 : 0;
-    if (const char* s = getenv("BH_BLOCKS_PER_CU")) g_ctx.opt_blocks_per_cu = std::min<int64_t>(std::max<int64_t>(0, atoll(s)), kMaxBlocksPerCu);
-    if (const char* s = getenv("BH_PCG_BATCH")) g_ctx.opt_batch = std::max<int64_t>(0, atoll(s));
-    if (const char* s = getenv("BH_PROJ_FORM")) g_ctx.opt_proj_form = atoll(s) ? 1 : 0;
-    if (const char* s = getenv("BH_CG_FUSED")) g_ctx.opt_cg_fused = std::min<int64_t>(std::max<int64_t>(0, atoll(s)), 2);
-    if (const char* s = getenv("BH_FINAL_SYNC")) g_ctx.opt_final_sync = atoll(s) ? 1 : 0;
-    if (const char* s = getenv("BH_FREE_IMAGE")) g_ctx.opt_free_image = std::min<int64_t>(std::max<int64_t>(0, atoll(s)), 2);
-    if (const char* s = getenv("BH_FREE_IMAGE_EQ")) g_ctx.opt_free_image_eq = atoll(s) != 0 ? 1 : 0;
-    if (const char* s = getenv("BH_CAUCHY_BLOCK")) { if (cauchy_block_value_ok(atoll(s))) g_ctx.opt_cauchy_block = atoll(s); }
+    options_from_env(g_ctx, getenv, kMaxBlocksPerCu);
     g_ctx.init = true;
     return BH_OK;
 }
@@ -1533,95 +1477,11 @@ int32_t bh_device_info(char* name_out, int64_t name_cap, int32_t* n_cu, char* ar
 }
 
 int32_t bh_set_option(const char* key, int64_t value) {
-    if (!key) return fail(BH_ERR_INVALID_ARG, "NULL key");
-    if (!strcmp(key, "blocks_per_cu")) {
-        if (value < 0 || value > kMaxBlocksPerCu) return fail(BH_ERR_INVALID_ARG, "blocks_per_cu must be 0 (default) .. 8");
-        g_ctx.opt_blocks_per_cu = value;
-        return BH_OK;
-    }
-    if (!strcmp(key, "pcg_batch")) { g_ctx.opt_batch = std::max<int64_t>(0, value); return BH_OK; }
-    if (!strcmp(key, "proj_form")) { g_ctx.opt_proj_form = value ? 1 : 0; return BH_OK; }
-    if (!strcmp(key, "fold_init")) { g_ctx.opt_fold_init = value ? 1 : 0; return BH_OK; }
-    if (!strcmp(key, "cg_fused")) {
-        if (value < 0 || value > 2) return fail(BH_ERR_INVALID_ARG, "cg_fused is 0, 1 (box constraints) or 2 (also linear equalities)");
-        g_ctx.opt_cg_fused = value;
-        return BH_OK;
-    }
-    if (!strcmp(key, "final_sync")) { g_ctx.opt_final_sync = value ? 1 : 0; return BH_OK; }
-    if (!strcmp(key, "host_copy_kernels")) { g_ctx.opt_host_copy_kernels = value ? 1 : 0; return BH_OK; }
-    if (!strcmp(key, "ls_from_cg")) { g_ctx.opt_ls_from_cg = value ? 1 : 0; return BH_OK; }
-    if (!strcmp(key, "step_from_cg")) { g_ctx.opt_step_from_cg = value ? 1 : 0; return BH_OK; }
-    if (!strcmp(key, "gram_mfma")) { g_ctx.opt_gram_mfma = value; return BH_OK; }
-    if (!strcmp(key, "chol_downdate")) { g_ctx.opt_chol_downdate = value ? 1 : 0; return BH_OK; }
-    if (!strcmp(key, "cauchy_image")) { g_ctx.opt_cauchy_image = value ? 1 : 0; return BH_OK; }
-    if (!strcmp(key, "cauchy_gram")) { g_ctx.opt_cauchy_gram = value ? 1 : 0; return BH_OK; }
-    if (!strcmp(key, "cauchy_gram_eq")) {
-        if (value != 0 && value != 1) return fail(BH_ERR_INVALID_ARG, "cauchy_gram_eq is 0 or 1");
-        g_ctx.opt_cauchy_gram_eq = value;
-        return BH_OK;
-    }
-    if (!strcmp(key, "gram_cg_fused")) {
-        // selects a device path of the product: like every product-path call it needs bh_init (switching it off never fails)
-        if (value != 0) BH_REQUIRE_INIT();
-        if (value != 0 && value != 1) return fail(BH_ERR_INVALID_ARG, "gram_cg_fused is 0 or 1");
-        g_ctx.opt_gram_cg_fused = value;
-        return BH_OK;
-    }
-    if (!strcmp(key, "cauchy_image_refresh")) {
-        if (value < 0) return fail(BH_ERR_INVALID_ARG, "cauchy_image_refresh is 0 (never) or the number of passes between two re-formations");
-        g_ctx.opt_cauchy_image_refresh = value;
-        return BH_OK;
-    }
-    if (!strcmp(key, "cauchy_fused")) { g_ctx.opt_cauchy_fused = value ? 1 : 0; return BH_OK; }
-    if (!strcmp(key, "cauchy_block")) {
-        if (!cauchy_block_value_ok(value)) return fail(BH_ERR_INVALID_ARG, "cauchy_block is 0, 1, 2, 4, 8 or 16 breakpoints per launch");
-        g_ctx.opt_cauchy_block = value;
-        return BH_OK;
-    }
-    if (!strcmp(key, "linv_refine")) { g_ctx.opt_linv_refine = value ? 1 : 0; return BH_OK; }
-    if (!strcmp(key, "cauchy_gemm")) { g_ctx.opt_cauchy_gemm = value ? 1 : 0; return BH_OK; }
-    if (!strcmp(key, "cauchy_image_max_ma")) { g_ctx.opt_cauchy_image_max_ma = std::min<int64_t>(std::max<int64_t>(0, value), 64); return BH_OK; }
-    if (!strcmp(key, "image_pool")) {
-        if (value < 0 || value > 8) return fail(BH_ERR_INVALID_ARG, "image_pool must be 0..8");
-        g_ctx.opt_image_pool = value;
-        while ((int64_t)g_ctx.image_pool.size() > value) { dev_free(g_ctx.image_pool.back().ptr); g_ctx.image_pool.pop_back(); }
-        return BH_OK;
-    }
-    if (!strcmp(key, "free_image")) {
-        if (value < 0 || value > 2) return fail(BH_ERR_INVALID_ARG, "free_image is 0 (off), 1 (by the policy) or 2 (build at the first eligible call)");
-        g_ctx.opt_free_image = value;
-        return BH_OK;
-    }
-    if (!strcmp(key, "free_image_minor")) {
-        if (value != 0 && value != 1) return fail(BH_ERR_INVALID_ARG, "free_image_minor is 0 or 1");
-        g_ctx.opt_free_image_minor = value;
-        return BH_OK;
-    }
-    if (!strcmp(key, "free_image_chain")) {
-        if (value != 0 && value != 1) return fail(BH_ERR_INVALID_ARG, "free_image_chain is 0 or 1");
-        g_ctx.opt_free_image_chain = value;
-        return BH_OK;
-    }
-    if (!strcmp(key, "free_image_eq")) {
-        if (value != 0 && value != 1) return fail(BH_ERR_INVALID_ARG, "free_image_eq is 0 or 1");
-        g_ctx.opt_free_image_eq = value;
-        return BH_OK;
-    }
-    if (!strcmp(key, "gram_ingest")) {
-        if (value != 0 && value != 1) return fail(BH_ERR_INVALID_ARG, "gram_ingest is 0 or 1");
-        g_ctx.opt_gram_ingest = value;
-        return BH_OK;
-    }
-    if (!strcmp(key, "upload_chunk_mb")) {
-        if (value < 1 || value > 4096) return fail(BH_ERR_INVALID_ARG, "upload_chunk_mb must be 1..4096");
-        g_ctx.opt_upload_chunk_mb = value;
-        return BH_OK;
-    }
-    if (!strcmp(key, "profile_stride")) {
-        if (value < 1) return fail(BH_ERR_INVALID_ARG, "profile_stride must be >= 1");
-        g_ctx.opt_ev_stride = value;
-        return BH_OK;
-    }
+    std::string why;
+    const int32_t rc = option_set(g_ctx, key, value, g_ctx.init, &why, kMaxBlocksPerCu);   // the table of bh_options.h
+    if (rc < BH_OK) return fail(rc, why);
+    while ((int64_t)g_ctx.image_pool.size() > g_ctx.opt_image_pool) { dev_free(g_ctx.image_pool.back().ptr); g_ctx.image_pool.pop_back(); }   // image_pool
+    if (rc != kOptionForCaller) return BH_OK;
     if (!strcmp(key, "comm_path")) {
         if (value == 1 && !g_ctx.peer.active) return fail(BH_ERR_PRECONDITION, "comm_path = 1 needs the peer-buffer communicator (BH_COMM=ipc or both)");
         if (value == 0 && comm_active() && g_ctx.comm == nullptr) return fail(BH_ERR_PRECONDITION, "comm_path = 0 needs an RCCL communicator (BH_COMM=rccl or both)");

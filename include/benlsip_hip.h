@@ -364,8 +364,10 @@ int32_t bh_stats_reset(bh_hess* H);
 /* Tuning knobs; unknown keys return BH_ERR_INVALID_ARG.  Defaults in brackets.  (A key whose A/B experiment is decided leaves
  * this list together with the losing path, and is an unknown key from then on.)
  *   "proj_form"      [1] 1 = reduced mA x mA projection (factor built on the device), 0 = the reference's augmented form
- *                        (needs the caller's factor in bh_proj_set_active)
- *   "pcg_batch"      [0] CG iterations enqueued per launch-ahead batch; 0 = by problem size (1 when an H*p streams >= 100 us)
+ *                        (needs the caller's factor in bh_proj_set_active).  Any non-zero value is 1.  Environment: BH_PROJ_FORM
+ *                        (read by bh_init, likewise)
+ *   "pcg_batch"      [0] CG iterations enqueued per launch-ahead batch; 0 = by problem size (1 when an H*p streams >= 100 us).
+ *                        A negative value is 0.  Environment: BH_PCG_BATCH (read by bh_init, likewise)
  *   "fold_init"      [1] box constraints: fold projected_cg's initialisation into the first H*p / step launches
  *   "cg_fused"       [1] shape of a CG iteration.  1 (default): box constraints in two kernels (the H*p launch forms p and takes the
  *                        exit test, one kernel reduces the slabs — exchanging them between the ranks of a peer-buffer communicator —
@@ -374,7 +376,8 @@ int32_t bh_stats_reset(bh_hess* H);
  *                        three kernels (H*p, reduce/update, projection with the explicit inverse of the reduced factor).
  *                        2: linear equalities in four kernels (triangular solves in a launch of their own); box as 1.
  *                        0: the round-1 shapes (three kernels box, seven with equalities; p'Hp = dot(p, H*p) exactly as the
- *                        reference forms it, where 1 and 2 form it as sum_i w_i (Jp)_i^2)
+ *                        reference forms it, where 1 and 2 form it as sum_i w_i (Jp)_i^2).  Another value: BH_ERR_INVALID_ARG.
+ *                        Environment: BH_CG_FUSED (read by bh_init; a value outside 0..2 is taken to its nearest end)
  *   "final_sync"     [0] device-pointer entry points (*_dev): 1 = always drain the library stream before returning, as the
  *                        host-pointer entry points do.  0 = return as soon as everything the HOST is owed has arrived; results
  *                        that stay in HBM are ordered on the library stream (later calls see them; bh_synchronize, or sharing
@@ -390,10 +393,12 @@ int32_t bh_stats_reset(bh_hess* H);
  *                          host nothing and return once their work is enqueued.
  *                        A caller's device vector is read where it lies when it needs no padding (n a multiple of 16, 16-byte
  *                        aligned); every other case, and every host-pointer entry point, behaves as before.
+ *                        Any non-zero value is 1.  Environment: BH_FINAL_SYNC (read by bh_init, likewise)
  *   "host_copy_kernels" [1] host-pointer entry points: the caller's vectors travel between the pinned arena and HBM by a small
  *                        copy kernel on the mapped arena instead of a DMA engine transfer, and the call ends with a mailbox seal +
  *                        poll instead of hipStreamSynchronize (bh_pcg 0.660 -> 0.652 ms, bh_minor_iterate 0.693 -> 0.665 ms,
- *                        bh_project 31 -> 21 us on the config-3 instance); 0 = DMA + synchronize (round 1)
+ *                        bh_project 31 -> 21 us on the config-3 instance); 0 = DMA + synchronize (round 1).  Any non-zero value
+ *                        is 1.  Environment: BH_HOST_COPY_KERNELS (read by bh_init, likewise)
  *   "ls_from_cg"     [1] bh_minor_iterate: w'Hw of the line search from the H*w the CG loop accumulated (0: explicit vthv)
  *   "step_from_cg"   [0] opt-in (the resident inner-step mirrors set it around their loop): bh_step_accumulate_dev called right
  *                        behind the bh_minor_iterate_dev that produced its w (same handle,
@@ -467,8 +472,9 @@ int32_t bh_stats_reset(bh_hess* H);
  *   "cauchy_gemm"    [1] B = J D A' in ONE sweep over J on the fp64 matrix cores (a tall-skinny GEMM: M = rows of J, N = mA, K = n);
  *                        0: mA J v sweeps over the masked rows of A
  *   "gram_mfma"      [1] A_free A_free' on fp64 MFMA when mA > 96 (2: always, 0: never)
- *   "blocks_per_cu"  [0] workgroups per CU of the row-streaming kernels (0: per-geometry default)
- *   "blocks_per_cu" accepts 0..8 (the partial-slab buffers hold 8 workgroups per CU); anything else is BH_ERR_INVALID_ARG
+ *   "blocks_per_cu"  [0] workgroups per CU of the row-streaming kernels (0: per-geometry default).  Accepts 0..8 (the partial-slab
+ *                        buffers hold 8 workgroups per CU); anything else is BH_ERR_INVALID_ARG.  Environment: BH_BLOCKS_PER_CU (read by
+ *                        bh_init; a value outside the range is taken to its nearest end)
  *   "comm_path"      [0 with BH_COMM=rccl|both, 1 with BH_COMM=ipc] which communicator carries the all-reduces: 0 = RCCL,
  *                        1 = the one-shot peer-buffer exchange fused into the slab reduction (needs BH_COMM=ipc or both)
  *   "profile"        [flags of bh_init] 1 = hipEvents around every profile_stride-th H*p launch (bh_stats: hmul_ms / hmul_timed)

@@ -134,7 +134,9 @@ def test_helpers_and_accepted_values(lines):
 
 def test_library_plumbs_the_option():
     api = open(os.path.join(CSRC, "bh_api.hip")).read()
-    assert '"cauchy_block"' in api and '"BH_CAUCHY_BLOCK"' in api and "cauchy_pass_rowspace_block" in api
+    options = open(os.path.join(CSRC, "bh_options.h")).read()       # the key and its environment variable: one row of the option table
+    assert '"cauchy_block"' in options and '"BH_CAUCHY_BLOCK"' in options and '#include "bh_options.h"' in api
+    assert "cauchy_pass_rowspace_block" in api
     assert "cauchy_block_pass_target(" in api and "cauchy_block_final_launch(" in api
     assert '"cauchy_block"' in open(os.path.join(ROOT, "include", "benlsip_hip.h")).read()
     hdr = open(os.path.join(CSRC, "bh_cauchy_plan.h")).read()

@@ -8,6 +8,7 @@ by the host compiler alone (address and undefined-behaviour sanitizers on), as t
   W and tpart present, the lineq image with the handle's leading dimension, a register-resident geometry, something to iterate on, g
   padded), one rank, the implicit form, atol_f2b > 0, the call not handed back, and no H*w wanted — whatever hw_free_part_ok says."""
 import os
+import re
 import shutil
 import subprocess
 
@@ -152,9 +153,12 @@ def test_the_library_follows_the_rule_and_the_stamp():
     release = api[api.index("static void free_image_release(bh_hess* H) {"):]
     release = release[:release.index("\n}\n")]
     assert "dev_free(H->Af)" in release and "H->af_epoch = 0" in release
-    lines = api.splitlines()
-    at = next(i for i, ln in enumerate(lines) if 'getenv("BH_FREE_IMAGE")' in ln)
-    assert 'getenv("BH_FREE_IMAGE_EQ")' in lines[at + 1]
+    # both variables are environment rows of the option table, which bh_init reads (what each does: tests/test_options_cpu.py)
+    options = re.sub(r"\s+", " ", open(os.path.join(CSRC, "bh_options.h")).read())
+    assert re.search(r'\{"free_image", &Options::opt_free_image, [^{}]*"BH_FREE_IMAGE", OPT_\w+\}', options)
+    assert re.search(r'\{"free_image_eq", &Options::opt_free_image_eq, [^{}]*"BH_FREE_IMAGE_EQ", OPT_\w+\}', options)
+    init = api[api.index("int32_t bh_init(int32_t device, int32_t flags) {"):api.index("int32_t bh_shutdown(void) {")]
+    assert "options_from_env(g_ctx, getenv, kMaxBlocksPerCu);" in init
     hdr = open(os.path.join(CSRC, "bh_pcg_plan.h")).read()
     fields = hdr[hdr.index("struct PcgSelectIn {"):hdr.index("struct PcgSelection {")]
     assert fields.rstrip().rstrip("};").rstrip().splitlines()[-1].lstrip().startswith("int64_t free_image_eq;")     # appended at the end
