@@ -117,15 +117,18 @@ def carried_search(J, C, mu, x, g, xlow, xupp, delta, refresh=0):
 # Exact instances: integer / dyadic data, every product, sum and quotient on the way exact in fp64 — the step is the same to the
 # last bit whatever the order of summation and however often the images are formed again.
 # ------------------------------------------------------------------------------------------------------------------------------
-def exact_instance(rows, n, q, npass, mu=0.5, mA=0, seed=0):
+def exact_instance(rows, n, q, npass, mu=0.5, mA=0, seed=0, order=None, theta_exp=13):
     """J~ = [J; C] with rows = d + q rows and entries in {-1, 0, 1} 2^-e, 2^e ~ sqrt(rows) (the q rows of C weighted by mu = 1/2);
     x = 0; g_i = -2^(-(i mod 3)), so d_i = 1, 1/2 or 1/4.  npass - 1 variables (a random choice) meet upper bounds one after the other
     at theta = 2^-13 (k + 1) <= 2^-6; every other bound is +-1024 and delta = 64, reached at theta >= 64.  The minimiser of a segment
     lies near ||d||^2 / d'Hd ~ 1/2 — between the two — so the search passes the npass - 1 breakpoints and ends inside the next
     segment (the CPU test checks the count with the oracle).  Every t_d, t_s, phi', phi'' is a dyadic rational of fewer than 50 bits:
     exact in fp64 in any order; the last step -phi'/phi'' is one correctly rounded quotient of two exact numbers.
-    With mA > 0 a matrix A with entries in {-1, 0, 1} is returned too (its projection is not dyadic)."""
-    assert npass - 1 <= min(127, n)
+    With mA > 0 a matrix A with entries in {-1, 0, 1} is returned too (its projection is not dyadic).
+    `order`: the explicit hitting order of the npass - 1 bounded variables (default: the random choice above, drawn either way so
+    that J~ does not depend on it).  `theta_exp` = t: breakpoints at 2^-t (k + 1), at most 2^(t - 6) - 1 of them so that the last
+    one stays at or below 2^-6 (the default 13 allows 127; tests/test_gram_cases_cpu.py proves 14 with 129 exact)."""
+    assert npass - 1 <= min(2 ** (theta_exp - 6) - 1, n)
     rng = np.random.default_rng(1000 + seed)
     d = rows - q
     e = int(round(0.5 * np.log2(rows)))
@@ -134,20 +137,24 @@ def exact_instance(rows, n, q, npass, mu=0.5, mA=0, seed=0):
     g = -(2.0 ** -(np.arange(n) % 3).astype(np.float64))
     x = np.zeros(n)
     xlow, xupp = -1024.0 * np.ones(n), 1024.0 * np.ones(n)
-    order = rng.permutation(n)[:max(npass - 1, 0)]
+    drawn = rng.permutation(n)[:max(npass - 1, 0)]
+    if order is None:
+        order = drawn
+    order = np.asarray(order, dtype=np.int64)
+    assert order.shape == (max(npass - 1, 0),) and np.unique(order).size == order.size and (order.size == 0 or (0 <= order.min() and order.max() < n))
     for k, i in enumerate(order):
-        xupp[i] = (2.0 ** -13) * (k + 1) * (-g[i])
+        xupp[i] = (2.0 ** -theta_exp) * (k + 1) * (-g[i])
     A = rng.integers(-1, 2, size=(mA, n)).astype(np.float64) if mA else np.zeros((0, n))
     return J, C, mu, A, x, g, xlow, xupp, 64.0
 
 
-def exact_equality_instance(rows, n, q, npass, mA, per_row=4, mu=0.5, seed=0):
+def exact_equality_instance(rows, n, q, npass, mA, per_row=4, mu=0.5, seed=0, theta_exp=13):
     """exact_instance with mA linear equalities that keep every quantity dyadic: the rows of A have disjoint supports of per_row (a
     power of 4) entries +-1 on variables that never reach a bound, so A_free A_free' = per_row I for the whole search — its Cholesky
     factor sqrt(per_row) I, the two solves, y = A(-g) / per_row, d = -D g - D A'y, a = J~ D g, B = J~ D A' and t_d = -a - B y are
     exact in fp64 whatever form (augmented or reduced projector, per-thread or tiled row body, GEMM or sweeps) computes them."""
     assert per_row in (4, 16) and mA * per_row + npass - 1 <= n
-    J, C, mu, _, x, g, xlow, xupp, delta = exact_instance(rows, n, q, npass, mu=mu, seed=seed)
+    J, C, mu, _, x, g, xlow, xupp, delta = exact_instance(rows, n, q, npass, mu=mu, seed=seed, theta_exp=theta_exp)
     rng = np.random.default_rng(2000 + seed)
     never_hit = np.flatnonzero(xupp == 1024.0)
     cols = rng.permutation(never_hit)[:mA * per_row].reshape(mA, per_row)
