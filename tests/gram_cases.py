@@ -161,7 +161,11 @@ def cg_placements(n, n_cu, bpc):
     run of CPT chunks inside the vector, and for the workgroup that owns the last run that holds an element (it owns as many runs
     as any): the first element of its first run, the last element of its last run (n - 1) and, where it owns several, the first
     element of its second run.  Edges that fall on one index are one placement."""
-    geo = cg_geometry(n, n_cu, bpc)
+    return placements_of(n, cg_geometry(n, n_cu, bpc))
+
+
+def placements_of(n, geo):
+    """cg_placements for a geometry given as CPT, grid and nruns (the row form has another grid: tests/cg_rows_cases.py)."""
     per_run = 2 * geo["CPT"]
     out = [(0, "index 0"), (1, "index 1"), (n - 1, "index n-1" + (", half of the last chunk" if n % 2 else ""))]
     mid = max(1, geo["nruns"] // 2)
@@ -191,8 +195,12 @@ KAPPA2 = 2.0 ** -10
 N_CU_DESIGN = (256, 304, 64, 8)          # grids the placements are designed for (any other device: asserted at run time)
 
 
-def _reserved(n):
-    return set(all_cg_indices(n, N_CU_DESIGN))
+def _reserved(n, reserve=()):
+    """The deciding indices of width n: the placements of gram_cg_kernel on the design grids and, for a caller that places cases
+    elsewhere (tests/cg_rows_cases.py: the grids of the row form), the indices it names.  reserve = () is the instance the Gram
+    module has always had."""
+    assert all(0 <= i < n for i in reserve)
+    return set(all_cg_indices(n, N_CU_DESIGN)) | set(reserve)
 
 
 def _spare(n, count, taken):
@@ -207,10 +215,11 @@ def _spare(n, count, taken):
 
 
 @functools.lru_cache(maxsize=None)
-def cg_instance(family, n):
+def cg_instance(family, n, reserve=()):
     """The shared part of a family at width n: J (n x n), C, mu, the dense G the oracle multiplies with, the fixed variables and
-    the gradient g0 before a case chooses its signs.  Built once per (family, n), read-only."""
-    taken = _reserved(n)
+    the gradient g0 before a case chooses its signs.  Built once per (family, n, reserve), read-only.  `reserve`: a sorted tuple
+    of further indices kept as deciding indices (_reserved)."""
+    taken = _reserved(n, reserve)
     fixed = _spare(n, 2, taken)
     fix = np.zeros(n, dtype=bool)
     fix[fixed] = True
@@ -266,16 +275,17 @@ def cg_instance(family, n):
     g0[fix] = 1.0                                                    # masked by the projection
     for arr in (J, C, G, fix, g0, q, cls):
         arr.setflags(write=False)
-    return CgInstance(family, n, LAM, J, C, mu, G, fix, g0, q, cls, tuple(sorted(_reserved(n))))
+    return CgInstance(family, n, LAM, J, C, mu, G, fix, g0, q, cls, tuple(sorted(_reserved(n, reserve))))
 
 
 def _p2_sign_c2(inst, i, c):
     return math.copysign(1.0, c * inst.q[i])                        # p_2 = -u + c q / 2, u_i = 0 at a deciding index
 
 
-def cg_case(family, n, index, kind, side, edge=""):
-    """One bounded case: g and the one finite bound.  p_2,i > 0 is stopped by w_u (side "upper"), p_2,i < 0 by w_l."""
-    inst = cg_instance(family, n)
+def cg_case(family, n, index, kind, side, edge="", inst=None):
+    """One bounded case: g and the one finite bound.  p_2,i > 0 is stopped by w_u (side "upper"), p_2,i < 0 by w_l.  `inst`: the
+    instance to place it on (default: cg_instance(family, n))."""
+    inst = cg_instance(family, n) if inst is None else inst
     want = 1.0 if side == "upper" else -1.0
     g = inst.g0.copy()
     if family == "C2":
@@ -301,10 +311,9 @@ def cg_case(family, n, index, kind, side, edge=""):
     return CgCase(family, n, index, kind, side, edge, g, w_l, w_u, KAPPA2)
 
 
-def short_case(family, n):
+def short_case(family, n, inst=None):
     """A one-iteration call for the same handle: the bound of variable 0 is met at gamma_1 = alpha_1 / 2."""
-    inst = cg_instance(family, n)
-    c = cg_case(family, n, 0, "half", "upper")
+    c = cg_case(family, n, 0, "half", "upper", inst=inst)
     alpha1 = 1.0 / (2.0 * LAM) if family == "C2" else 0.25 / LAM
     p1 = -c.g[0]
     w_l, w_u = np.full(n, -np.inf), np.full(n, np.inf)
@@ -339,15 +348,22 @@ def cg_model(M, g, fix, w_l, w_u, kappa2, led, atol=SQRT_EPS, atol_f2b=1e-10):
     while not solved and not outside and not neg and it <= max_iter:
         Hp = led.matvec(M, p, "G p")
         pHp = led.dot(p, Hp, "p'Hp")
-        assert pHp > atol                                            # (no case of these families meets negative curvature)
-        rtv = led.dot(r, v, "r.v")
-        alpha = led.quotient(rtv, pHp, "alpha")
         gamma = math.inf
         for i in np.flatnonzero((np.abs(p) >= atol_f2b) & np.isfinite(np.where(p > 0, w_u, w_l))):
             wb = w_u[i] if p[i] > 0 else w_l[i]
             num = wb - w[i]
             assert Fraction(num) == Fraction(wb) - Fraction(w[i])
             gamma = min(gamma, led.quotient(num, p[i], "gamma"))
+        if pHp <= atol:                                              # :725 (only with an atol or a mu of the caller's: the
+            neg = True                                               # families of this module never get here)
+            if abs(pHp) > atol:                                      # :727
+                w = led.axpy(gamma, p, w, "w")
+                rows.append((pHp, math.nan, gamma, rtv))
+            else:
+                rows.append((pHp, math.nan, math.nan, rtv))
+            break
+        rtv = led.dot(r, v, "r.v")
+        alpha = led.quotient(rtv, pHp, "alpha")
         outside = alpha > gamma
         if outside:
             w = led.axpy(gamma, p, w, "w")
@@ -362,19 +378,22 @@ def cg_model(M, g, fix, w_l, w_u, kappa2, led, atol=SQRT_EPS, atol_f2b=1e-10):
             solved = abs(rtv) < tol_cg
             it += 1
         rows.append((pHp, alpha, gamma, rtv))
-    status = R.CGStatus.solved if solved else R.CGStatus.bound_hit if outside else (R.CGStatus.max_iter_reached if it == max_iter else R.CGStatus.none)
+    status = (R.CGStatus.solved if solved else R.CGStatus.bound_hit if outside else R.CGStatus.negative_curvature if neg else
+              R.CGStatus.max_iter_reached if it == max_iter else R.CGStatus.none)
     return w, int(status), it, np.array(rows).reshape(-1, 4)
 
 
-def cg_oracle(case):
+def cg_oracle(case, inst=None, atol=SQRT_EPS, G=None):
     """The oracle's projected_cg on a case with its Gram-form H*v: (J'J + mu C'C) @ p with the matrix formed first — here handed
     over (cg_instance's G; tests/test_gram_cases_cpu.py checks it against J'J + mu C'C), because J'J of an 8200 x 8200 J costs
-    more than the whole suite.  Returns (w, status, iters, trace rows)."""
-    inst = cg_instance(case.family, case.n)
+    more than the whole suite.  Returns (w, status, iters, trace rows).  `inst`, `G`: the instance the case was placed on and its
+    matrix (default: cg_instance(case.family, case.n) and its G); `atol`: the curvature threshold (:711)."""
+    inst = cg_instance(case.family, case.n) if inst is None else inst
+    G = inst.G if G is None else G
     Ho = R.AlHessian(inst.J, inst.C, inst.mu)
     cons = R.make_mixed_constraints(np.zeros((0, case.n)), R.chol_lower(np.zeros((0, 0))), inst.fix)
     tr = R.CGTrace()
-    w, st, it = R.projected_cg(case.g, Ho, case.w_l, case.w_u, cons, case.kappa2, hmul_fn=lambda H, v: inst.G @ v, trace=tr)
+    w, st, it = R.projected_cg(case.g, Ho, case.w_l, case.w_u, cons, case.kappa2, atol=atol, hmul_fn=lambda H, v: G @ v, trace=tr)
     return w, int(st), int(it), np.array(tr.rows).reshape(-1, 4)
 
 
