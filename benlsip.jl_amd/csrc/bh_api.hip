@@ -9,6 +9,7 @@
 #include "bh_launch_ahead.h"
 #include "bh_options.h"
 #include "bh_pcg_plan.h"
+#include "bh_gram_read_plan.h"
 #include "bh_step_chain_plan.h"
 
 #include <dlfcn.h>
@@ -160,6 +161,7 @@ struct Ctx : Options {   // the opt_* fields of bh_set_option: bh_options.h
     bool reform_vlds_attr_set = false;   // cauchy_reform_kernel<512,16,1,VL>
     bool vlds_attr_set = false;      // row_stream_kernel<512,16,1,FUSED,...,VL>
     bool cgp_vlds_attr_set = false;  // ... and its two CG-prologue symbols
+    bool gramsym_vlds_attr_set = false;  // gram_symv_kernel<512,8,2,0,VL>
     bool trsm_lds_granted = false;   // chol_trsm_kernel
     size_t trsv_lds_granted = 0;     // trsv_pair_kernel
 };
@@ -361,6 +363,29 @@ void launch_gram_cg(int cfg, const RowStreamArgs& a, int grid, hipStream_t s, bo
     });
 }
 
+// Gram form read through the lower triangle (bh_gramsym.hip.h): the register-resident geometries over the n rows of G, n <= 8192.
+// The product keeps its slice of v next to z and both row buffers: in registers up to n = 4096, in LDS (VL, 64 KiB, asked for once)
+// for 4096 < n <= 8192, where the registers alone spill; the quadratic form has no z and needs no LDS.
+// kGramSymLastGeomOk: whether the widest geometry (8192 < n <= 16384) is served.  Its product kernel spills even with v in LDS
+// (profiles/r23_gram_read_resources.txt), so it is not instantiated and such handles keep the full read.
+constexpr bool kGramSymLastGeomOk = false;
+void launch_gram_symv(int cfg, bool quad, const GramSymArgs& a, int grid, hipStream_t s) {
+    with_rs_geom(cfg, [&](auto geom) {
+        using G = decltype(geom);
+        if constexpr (!G::vec_in_lds || kGramSymLastGeomOk) {
+            if (quad) {
+                hipLaunchKernelGGL((gram_symv_kernel<G::T, G::CPT, G::R, 1>), dim3(grid), dim3(G::T), 0, s, a);
+                return;
+            }
+            constexpr int VL = G::vec_bytes >= 64 * 1024 ? 1 : 0;
+            constexpr size_t lds = VL ? G::vec_bytes : 0;
+            auto* kernel = &gram_symv_kernel<G::T, G::CPT, G::R, 0, VL>;
+            if constexpr (VL != 0) grant_lds_once(g_ctx.gramsym_vlds_attr_set, lds, {reinterpret_cast<const void*>(kernel)});
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(G::T), lds, s, a);
+        }
+    });
+}
+
 int grid_for(int cfg, int64_t nrows) {
     const RsConfig& c = kRsConfigs[cfg];
     const int64_t ngroups = (nrows + c.R - 1) / c.R;
@@ -422,6 +447,10 @@ struct bh_hess {
     int64_t gram_builds = 0;
     double* geq = nullptr;         // (1 + mA) x ld: a = G D g and B = G D A' of the Cauchy search with equalities from G (lazy, grown on demand)
     int64_t geq_doubles = 0;
+    // how the Gram form reads G (bh_hess_set_gram_read, bh_gram_read_plan.h): remembered in either form, never rebuilds G
+    int gram_read = GRAM_READ_FULL;
+    int64_t products_lower = 0;    // launches of gram_symv_kernel<..., QUAD = 0> since the handle was created
+    int64_t quads_from_g = 0;      // launches of gram_symv_kernel<..., QUAD = 1>
     // compact image of the free columns (option free_image; bh_free_image_plan.h, bh_freeimg.hip.h)
     double* Jf = nullptr;          // (d + q_eff) x fi.ldf row-major, from the image pool
     int64_t Jf_doubles = 0;        // capacity of the allocation behind Jf
@@ -652,8 +681,17 @@ int32_t profile_begin(bh_hess* H, int ev_index, int* slot) {
     return BH_OK;
 }
 
+// Which path a call of kind `call` (GramReadCall) takes on this handle now (bh_gram_read_plan.h).
+bool gram_served(const bh_hess* H) { return gram_read_served(H->nchunks, kMaxChunks, kGramSymLastGeomOk); }
+GramReadPath gram_path(const bh_hess* H, int call) {
+    GramReadIn in{};
+    in.mode = H->gram_read; in.gram_form = H->form == BH_HESS_GRAM; in.served = gram_served(H); in.call = call;
+    return gram_read_path(in);
+}
+
 // Algorithmic bytes of one H*p launch in the handle's current form (bh_stats_t.bytes_per_hmul).
 double hmul_bytes(const bh_hess* H) {
+    if (gram_path(H, GRAM_CALL_PRODUCT) == GRAM_PATH_LOWER) return gram_read_lower_bytes(H->n) + 16.0 * (double)H->n;
     if (H->form == BH_HESS_GRAM) return 8.0 * (double)H->n * (double)H->ld + 16.0 * (double)H->n;
     return (multi_panel(H) ? 16.0 : 8.0) * (double)(H->d + H->q_eff) * (double)H->n + 16.0 * (double)H->n;
 }
@@ -711,13 +749,41 @@ void launch_gram_gv(bh_hess* H, const double* v_pad, double* z_out, const CgStat
     launch_row_stream(cfg, MODE_JV, a, grid_for(cfg, a.nrows), g_ctx.stream);
 }
 
+// G·v from the lower triangle (bh_hess_set_gram_read): gram_symv_kernel leaves one slab per workgroup in H->partials, the slab
+// reduction of the row-stream kernels sums them in index order.  A Gram handle lives on one rank: no exchange behind the reduction.
+void launch_gram_gv_lower(bh_hess* H, const double* v_pad, double* z_out, const CgState* state, bool negate, const int* negmask) {
+    GramSymArgs a{};
+    a.G = H->G; a.ld = H->ld; a.nrows = H->n; a.nchunks = H->nchunks; a.v = v_pad; a.partials = H->partials; a.state = state;
+    a.negate = negate ? 1 : 0; a.negmask = negmask;
+    const int cfg = pick_config(H->nchunks);
+    const int grid = grid_for(cfg, a.nrows);
+    launch_gram_symv(cfg, false, a, grid, g_ctx.stream);
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3((H->nchunks + kPeerBlockChunks - 1) / kPeerBlockChunks), dim3(256), 0, g_ctx.stream,
+                       H->partials, H->ld, H->nchunks, grid, z_out, state);
+    H->products_lower += 1;
+}
+
+// v'Gv from the lower triangle -> sq_out_scalar, where launch_jv would have left sum_i w_i (J v)_i^2: one launch over G and the
+// index-order fold of the per-workgroup partials.
+void launch_gram_quad(bh_hess* H, const double* v_pad, double* sq_out_scalar) {
+    GramSymArgs a{};
+    a.G = H->G; a.ld = H->ld; a.nrows = H->n; a.nchunks = H->nchunks; a.v = v_pad; a.sq_partials = H->sq_partials;
+    const int cfg = pick_config(H->nchunks);
+    const int grid = grid_for(cfg, a.nrows);
+    launch_gram_symv(cfg, true, a, grid, g_ctx.stream);
+    hipLaunchKernelGGL(reduce_scalar_kernel, dim3(1), dim3(256), 0, g_ctx.stream, H->sq_partials, grid, sq_out_scalar);
+    H->quads_from_g += 1;
+}
+
 // Gram form of launch_hmul: G rebuilt first when stale, then ONE launch — no slab reduction, no all-reduce.
+// (BH_GRAM_READ_LOWER on a served width: the lower triangle and the slab reduction, two launches.)
 int32_t launch_gram_hmul(bh_hess* H, const double* v_pad, double* z_out, const CgState* state, int ev_index, bool negate,
                          const int* negmask) {
     BH_TRY(ensure_gram(H));
     int slot = -1;
     BH_TRY(profile_begin(H, ev_index, &slot));
-    launch_gram_gv(H, v_pad, z_out, state, negate, negmask);
+    if (gram_path(H, GRAM_CALL_PRODUCT) == GRAM_PATH_LOWER) launch_gram_gv_lower(H, v_pad, z_out, state, negate, negmask);
+    else launch_gram_gv(H, v_pad, z_out, state, negate, negmask);
     if (slot >= 0) BH_HIP(hipEventRecord(H->ev[2 * slot + 1], g_ctx.stream));
     BH_HIP(hipGetLastError());
     return BH_OK;
@@ -771,6 +837,22 @@ int32_t launch_jv(bh_hess* H, const double* v_pad, double* t_out, bool with_c_ro
         hipLaunchKernelGGL(reduce_scalar_kernel, dim3(1), dim3(256), 0, g_ctx.stream, H->sq_partials, grid, sq_out_scalar);
     }
     BH_HIP(hipGetLastError());
+    return BH_OK;
+}
+
+// v'Hv -> H->scalar (vthv): the weighted square sum of a sweep over J (stats.n_jv) or, under BH_GRAM_READ_LOWER_QUAD on a Gram
+// handle, v'Gv from one launch over the lower triangle (quads_from_g).  The value is used exactly where the sweep's was.
+int32_t launch_quad(bh_hess* H, const double* v_pad) {
+    if (gram_path(H, GRAM_CALL_QUAD) == GRAM_PATH_QUAD_FROM_G) {
+        BH_TRY(hess_ready(H));
+        BH_TRY(ensure_gram(H));
+        launch_gram_quad(H, v_pad, H->scalar);
+        BH_HIP(hipGetLastError());
+        return BH_OK;
+    }
+    BH_TRY(launch_jv(H, v_pad, nullptr, true, H->scalar));
+    BH_TRY(allreduce_inplace(H->scalar, 1, H));
+    H->stats.n_jv += 1;
     return BH_OK;
 }
 
@@ -1448,7 +1530,7 @@ int32_t bh_shutdown(void) {
     if (g_ctx.own_stream) (void)hipStreamDestroy(g_ctx.own_stream);
     g_ctx.own_stream = nullptr; g_ctx.stream = nullptr;
     if (g_pin.base) { (void)hipHostFree(g_pin.base); g_pin = PinArena(); }
-    g_ctx.vlds_attr_set = false; g_ctx.cgp_vlds_attr_set = false; g_ctx.reform_vlds_attr_set = false; g_ctx.trsm_lds_granted = false; g_ctx.trsv_lds_granted = 0;
+    g_ctx.vlds_attr_set = false; g_ctx.cgp_vlds_attr_set = false; g_ctx.gramsym_vlds_attr_set = false; g_ctx.reform_vlds_attr_set = false; g_ctx.trsm_lds_granted = false; g_ctx.trsv_lds_granted = 0;
     g_ctx.init = false; g_ctx.rank = 0; g_ctx.nranks = 1;
     return BH_OK;
 }
@@ -1977,6 +2059,28 @@ int32_t bh_hess_get_form(const bh_hess* H, int32_t* form, int64_t* gram_builds) 
     return BH_OK;
 }
 
+int32_t bh_hess_set_gram_read(bh_hess* H, int32_t mode) {
+    if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
+    if (!gram_read_mode_ok(mode)) return fail(BH_ERR_INVALID_ARG, "mode is BH_GRAM_READ_FULL (0), BH_GRAM_READ_LOWER (1) or BH_GRAM_READ_LOWER_QUAD (2)");
+    if (mode == H->gram_read) return BH_OK;
+    const double before = hmul_bytes(H);
+    H->gram_read = mode;
+    if (hmul_bytes(H) != before) {              // the bytes a product streams changed: the mean over sampled launches starts again
+        H->stats.bytes_per_hmul = hmul_bytes(H);
+        H->timed_bytes = 0.0; H->timed_n = 0;
+    }
+    return BH_OK;
+}
+
+int32_t bh_hess_get_gram_read(const bh_hess* H, int32_t* mode, int32_t* served, int64_t* products_lower, int64_t* quads_from_g) {
+    if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
+    if (mode) *mode = H->gram_read;
+    if (served) *served = gram_served(H) ? 1 : 0;
+    if (products_lower) *products_lower = H->products_lower;
+    if (quads_from_g) *quads_from_g = H->quads_from_g;
+    return BH_OK;
+}
+
 int32_t bh_hess_free_image_info(const bh_hess* H, const bh_proj* P, int32_t* state, int64_t* width, int64_t* builds, int64_t* moves,
                                 int64_t* calls_served) {
     if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
@@ -2070,11 +2174,9 @@ int32_t bh_vthv(bh_hess* H, const double* v, double* out_scalar) {
     BH_REQUIRE_INIT();
     if (!H || !v || !out_scalar) return fail(BH_ERR_INVALID_ARG, "NULL argument");
     BH_TRY(stage_vec(H->vpad, v, H->n, false));
-    BH_TRY(launch_jv(H, H->vpad, nullptr, true, H->scalar));
-    BH_TRY(allreduce_inplace(H->scalar, 1, H));
+    BH_TRY(launch_quad(H, H->vpad));
     BH_TRY(fetch_vec(out_scalar, H->scalar, 1, false));
     BH_TRY(sync_flush());
-    H->stats.n_jv += 1;
     return BH_OK;
 }
 
@@ -3008,9 +3110,7 @@ static int32_t launch_linesearch(bh_hess* H, bh_proj* P, const double* g_dev, do
                                  bool scale_w, double* hw = nullptr, double* alpha_dst = nullptr /* default: c.scalars[0] */) {
     CgWorkspace& c = g_ctx.cg;
     if (hw == nullptr) {
-        BH_TRY(launch_jv(H, w_pad, nullptr, true, H->scalar));
-        BH_TRY(allreduce_inplace(H->scalar, 1, H));
-        H->stats.n_jv += 1;
+        BH_TRY(launch_quad(H, w_pad));
     }
     hipLaunchKernelGGL(linesearch_kernel, dim3(1), dim3(CG_T), 0, g_ctx.stream, g_dev, w_pad, wl_dev, wu_dev,
                        P->nfix > 0 ? P->fixrank : (const int*)nullptr, (const double*)H->scalar, hw, (int)H->n, scale_w ? 1 : 0,
@@ -3386,15 +3486,13 @@ int32_t bh_model_reduction_dev(bh_hess* H, const double* g_dev, const double* s_
     }
     const double* sp = H->vpad;
     BH_TRY(device_operand(&sp, H->vpad, s_dev, H->n, H->ld));
-    BH_TRY(launch_jv(H, sp, nullptr, true, H->scalar));
-    BH_TRY(allreduce_inplace(H->scalar, 1, H));
+    BH_TRY(launch_quad(H, sp));
     hipLaunchKernelGGL(vec_dot_kernel, dim3(1), dim3(CG_T), 0, g_ctx.stream, g_dev, s_dev, (int)H->n, c.scalars + 1);
     BH_HIP(hipGetLastError());
     BH_TRY(mbox_ensure());
     // s'Hs (all-reduced, so it lives in device memory) and g's ride to the host with the seal
     BH_TRY(mbox_seal_and_wait(2 * sizeof(double), H->scalar, c.scalars + 1, mbox_dev<double>(kMbScal)));
     const double vthv = mbox_host<double>(kMbScal)[0], gs = mbox_host<double>(kMbScal)[1];
-    H->stats.n_jv += 1;
     *out = gs + 0.5 * vthv;
     return BH_OK;
 }
@@ -4004,9 +4102,10 @@ int32_t bh_stats_reset(bh_hess* H) {
 
 int32_t bh_time_kernel(bh_hess* H, int32_t kind, int32_t reps, double* avg_ms) {
     BH_REQUIRE_INIT();
-    if (!H || !avg_ms || reps < 1 || kind < 0 || kind > 10) return fail(BH_ERR_INVALID_ARG, "bad argument");
+    if (!H || !avg_ms || reps < 1 || kind < 0 || kind > 11) return fail(BH_ERR_INVALID_ARG, "bad argument");
     BH_TRY(hess_ready(H));
-    if (kind >= 9 && H->form != BH_HESS_GRAM) return fail(BH_ERR_PRECONDITION, "bh_time_kernel(9, 10): the handle is not in the Gram form");
+    if (kind >= 9 && H->form != BH_HESS_GRAM) return fail(BH_ERR_PRECONDITION, "bh_time_kernel(9, 10, 11): the handle is not in the Gram form");
+    if (kind == 11 && !gram_served(H)) return fail(BH_ERR_PRECONDITION, "bh_time_kernel(11): no lower-triangle kernel for this width");
     if (kind == 7 && !comm_active()) return fail(BH_ERR_PRECONDITION, "bh_time_kernel(7): no communicator (bh_comm_init; BH_FORCE_COMM=1 for one rank)");
     struct EventPair {          // destroyed on every way out of this function
         hipEvent_t a = nullptr, b = nullptr;
@@ -4016,11 +4115,16 @@ int32_t bh_time_kernel(bh_hess* H, int32_t kind, int32_t reps, double* avg_ms) {
     BH_HIP(hipEventCreate(&evp.b));
     const hipEvent_t e0 = evp.a, e1 = evp.b;
     if (kind >= 9) {
-        // 9: a build of G (every launch a real build: gram_builds counts them); 10: one G·v launch
+        // 9: a build of G (every launch a real build: gram_builds counts them); 10: the product G·v the handle performs now (all
+        // of G in one launch, or the lower triangle and the slab reduction); 11: one quadratic form from G
         BH_TRY(ensure_gram(H));
+        const int64_t pl = H->products_lower, qg = H->quads_from_g;       // (the counters count the library's own launches)
+        struct Restore { bh_hess* H; int64_t pl, qg; ~Restore() { H->products_lower = pl; H->quads_from_g = qg; } } restore{H, pl, qg};
         auto one = [&]() -> int32_t {
             if (kind == 9) return launch_gram_build(H);
-            launch_gram_gv(H, H->vpad, H->zpad, nullptr, false, nullptr);
+            if (kind == 11) launch_gram_quad(H, H->vpad, H->scalar);
+            else if (gram_path(H, GRAM_CALL_PRODUCT) == GRAM_PATH_LOWER) launch_gram_gv_lower(H, H->vpad, H->zpad, nullptr, false, nullptr);
+            else launch_gram_gv(H, H->vpad, H->zpad, nullptr, false, nullptr);
             BH_HIP(hipGetLastError());
             return BH_OK;
         };

@@ -1,7 +1,8 @@
 // bh_gngram.hip.h — the explicit Gram form of the Gauss-Newton Hessian (bh_hess_set_form, BH_HESS_GRAM):
 // G = sum_r w_r J_r' J_r  (w_r = 1 for the rows of J, mu for the rows of C) over the row-major padded image, on fp64 MFMA.
 // Part of the single translation unit of bh_api.hip (see bh_kernels.hip.h for the layout and design notes).
-// G·v itself is row_stream_kernel<..., MODE_JV, ...> over the G image (bh_api.hip: launch_gram_hmul).
+// G·v itself is row_stream_kernel<..., MODE_JV, ...> over the G image (bh_api.hip: launch_gram_hmul), or under bh_hess_set_gram_read
+// gram_symv_kernel over its lower triangle (bh_gramsym.hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

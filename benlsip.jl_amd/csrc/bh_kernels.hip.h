@@ -29,4 +29,5 @@
 #include "bh_minor.hip.h"
 #include "bh_gngram.hip.h"
 #include "bh_gramcg.hip.h"
+#include "bh_gramsym.hip.h"
 #include "bh_freeimg.hip.h"

@@ -160,6 +160,41 @@ class AlHessian:
         """How many times G has been built on this handle (``bh_hess_get_form``)."""
         return self._get_form()[1]
 
+    _GRAM_READS = {"full": _lib.BH_GRAM_READ_FULL, "lower": _lib.BH_GRAM_READ_LOWER, "lower+quad": _lib.BH_GRAM_READ_LOWER_QUAD}
+
+    def set_gram_read(self, mode):
+        """``bh_hess_set_gram_read``: how the Gram form reads G — "full" (the default), "lower" (products read the lower triangle
+        only) or "lower+quad" (... and vthv, the line search and the swept model reduction take v'Gv from G instead of sweeping J;
+        the value can come out <= 0 near zero, which ||Jv||^2 cannot).  Remembered in either form; never rebuilds G."""
+        if mode not in self._GRAM_READS:
+            raise ValueError("gram read mode is 'full', 'lower' or 'lower+quad', got %r" % (mode,))
+        check(_lib.lib().bh_hess_set_gram_read(self._h, self._GRAM_READS[mode]), "bh_hess_set_gram_read")
+
+    def _get_gram_read(self):
+        m, s, p, q = ct.c_int32(0), ct.c_int32(0), ct.c_int64(0), ct.c_int64(0)
+        check(_lib.lib().bh_hess_get_gram_read(self._h, ct.byref(m), ct.byref(s), ct.byref(p), ct.byref(q)), "bh_hess_get_gram_read")
+        return m.value, s.value, p.value, q.value
+
+    @property
+    def gram_read(self):
+        """"full", "lower" or "lower+quad" (``bh_hess_get_gram_read``)."""
+        return {v: k for k, v in self._GRAM_READS.items()}[self._get_gram_read()[0]]
+
+    @property
+    def gram_read_served(self):
+        """Whether the handle's width has a lower-triangle kernel (``bh_hess_get_gram_read``)."""
+        return bool(self._get_gram_read()[1])
+
+    @property
+    def products_lower(self):
+        """Products G·v served from the lower triangle since the handle was created (``bh_hess_get_gram_read``)."""
+        return self._get_gram_read()[2]
+
+    @property
+    def quads_from_g(self):
+        """Quadratic forms v'Gv served from G since the handle was created (``bh_hess_get_gram_read``)."""
+        return self._get_gram_read()[3]
+
     def __mul__(self, v):
         return hmul(self, v)
 
@@ -191,7 +226,7 @@ class AlHessian:
     def time_kernel(self, kind, reps=20):
         """Average hipEvent milliseconds of one launch: kind 0 = fused J'(Jp), 1 = J v, 2 = J'u, 3..6 = read-only stream probe with 1/2/4/8 workgroups per CU,
         7 = all-reduce of one n-vector, 8 = slab reduction (+ exchange) of an H*p; Gram form only (``set_form("gram")``): 9 = a build of G,
-        10 = one G·v launch."""
+        10 = the product G·v the handle performs now (``set_gram_read``), 11 = one quadratic form v'Gv from the lower triangle."""
         ms = ct.c_double(0.0)
         check(_lib.lib().bh_time_kernel(self._h, kind, reps, ct.byref(ms)), "bh_time_kernel")
         return ms.value

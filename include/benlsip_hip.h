@@ -181,17 +181,47 @@ int32_t bh_hess_destroy(bh_hess* H);
  *   Hd = G d once, then one row of G per breakpoint inside ONE launch (cauchy_gram_kernel); with option "cauchy_gram_eq" = 1 the
  *   search with 1..64 linear equalities (one rank): Hd = -a - B y from a = G D g (n) and B = G D A' (n x mA), one row of G per
  *   breakpoint, a and B formed again from G every 128th pass (cauchy_gram_eq_kernel; bh_cauchy_info form 4).
- *   Still reading J: vthv(H, v) — src/basic_tralcnlss.jl:92-96 and bh_linesearch (||Jv||^2_W, never negative), bh_jv, bh_jtv,
+ *   Still reading J: vthv(H, v) — src/basic_tralcnlss.jl:92-96 and bh_linesearch (||Jv||^2_W, never negative; from G instead only
+ *   under BH_GRAM_READ_LOWER_QUAD, bh_hess_set_gram_read below), bh_jv, bh_jtv,
  *   bh_grad, and the row-space Cauchy search (cauchy_image = 1; with box constraints only while "cauchy_gram" = 0, with up to
  *   64 equalities only while "cauchy_gram_eq" = 0).
  * bh_hess_set_form: setting the current form is a no-op; BH_HESS_IMPLICIT frees G; BH_ERR_INVALID_ARG for another value;
  * BH_ERR_UNSUPPORTED for n > 16384 (G would exceed 2 GiB) or while a communicator with more than one rank is active; a failed
  * allocation returns BH_ERR_HIP and leaves the handle in the implicit form.  While the Gram form is on, stats.bytes_per_hmul is
- * 8 n ld + 16 n.  bh_hess_get_form: the current form and how many times G has been built on this handle. */
+ * 8 n ld + 16 n (the full read).  bh_hess_get_form: the current form and how many times G has been built on this handle. */
 #define BH_HESS_IMPLICIT 0
 #define BH_HESS_GRAM     1
 int32_t bh_hess_set_form(bh_hess* H, int32_t form);
 int32_t bh_hess_get_form(const bh_hess* H, int32_t* form, int64_t* gram_builds);
+/* How a handle in the Gram form reads G, which is bitwise symmetric.  Opt-in per handle, next to bh_hess_set_form; no option key.
+ *   BH_GRAM_READ_FULL        the default: every path, launch, counter and bit is what it is without this switch.
+ *   BH_GRAM_READ_LOWER       every product G·v that goes through the one product launcher (bh_hmul*, bh_hmul_add*, the sweep path of
+ *                            bh_step_accumulate_dev, the separate-kernel CG loop, the G d of "cauchy_gram", the a = G D g of
+ *                            "cauchy_gram_eq", the H*d form of the Cauchy search) reads the elements G_ij, j <= i, only: one launch
+ *                            over the lower triangle (gram_symv_kernel: row sums t_i = sum_{j<=i} G_ij v_j and the transposed
+ *                            contributions v_i G_ij, one slab per workgroup) and the slab reduction — two launches, every sum in a
+ *                            fixed order, no atomics.  The operator is the same, its rounding moves (other summation order).
+ *                            stats.bytes_per_hmul becomes 16 * (number of 16-byte chunks 0 .. i/2 of the rows i < n) + 16 n; the
+ *                            slab traffic is not counted.  gram_cg_kernel ("gram_cg_fused"), cauchy_gram_kernel and
+ *                            cauchy_gram_eq_kernel need contiguous whole rows and keep reading them: G stays stored in full.
+ *   BH_GRAM_READ_LOWER_QUAD  ... and the calls that end in vthv's weighted square sum — bh_vthv, bh_linesearch(_dev),
+ *                            bh_minor_iterate* with ls_from_cg = 0, bh_model_reduction_dev where it would sweep — take v'Gv from ONE
+ *                            launch over the lower triangle (q_i = v_i (2 sum_{j<i} G_ij v_j + G_ii v_i), one partial per
+ *                            workgroup, folded in index order) instead of a sweep over J: stats.n_jv does not grow on them,
+ *                            quads_from_g does.  The value is used exactly where vthv's was; no branch is added.  What is lost:
+ *                            ||Jv||^2_W is a sum of squares and never negative, while v'Gv is the same number rounded differently
+ *                            and can come out <= 0 where the true value is near zero (a direction almost in the null space of J).
+ *                            That is why this is a mode of its own and not part of BH_GRAM_READ_LOWER.
+ * bh_hess_set_gram_read may be called in either form: the mode is remembered and takes effect while the handle is in the Gram form.
+ * It never rebuilds G and raises no event on the step-chain notes.  NULL handle or a mode outside 0..2: BH_ERR_INVALID_ARG, the
+ * handle keeps its mode.  bh_hess_get_gram_read: the mode; served = 1 when the handle's width has a lower-triangle kernel (n <= 8192:
+ * for 8192 < n <= 16384 the product kernel does not fit the register file; a handle that is not served keeps the full read and the sweep over J under every mode, both counters stay 0);
+ * products_lower / quads_from_g = launches of the two lower-triangle forms since the handle was created.  Any pointer may be NULL. */
+#define BH_GRAM_READ_FULL        0
+#define BH_GRAM_READ_LOWER       1
+#define BH_GRAM_READ_LOWER_QUAD  2
+int32_t bh_hess_set_gram_read(bh_hess* H, int32_t mode);
+int32_t bh_hess_get_gram_read(const bh_hess* H, int32_t* mode, int32_t* served, int64_t* products_lower, int64_t* quads_from_g);
 int32_t bh_hess_shape(const bh_hess* H, int64_t* d, int64_t* n, int64_t* q);
 /* The compact image of the free columns (option "free_image"): one row per row of the image of J, only the columns of the
  * variables that are free, dense; the box-constrained CG loop of bh_pcg* streams it instead of J.
@@ -555,8 +585,11 @@ int32_t bh_set_option(const char* key, int64_t value);
  * non-temporal loads and adds) with 1, 2, 4, 8 workgroups per CU: the practical single-read ceiling the kernels are
  * quoted against; 7 = the all-reduce of one n-vector on the active communicator path (every rank must call it together);
  * 8 = everything an H*p does after its streaming kernel (slab reduction + all-reduce; without a communicator: the slab
- * reduction alone); 9 = a build of the Gram matrix G (each one counted by bh_hess_get_form), 10 = one G·v launch — both
- * BH_ERR_PRECONDITION unless the handle is in the Gram form (bh_hess_set_form).  Returns the average milliseconds per launch. */
+ * reduction alone); 9 = a build of the Gram matrix G (each one counted by bh_hess_get_form), 10 = the product G·v the handle
+ * performs now (one launch over all of G, or under BH_GRAM_READ_LOWER the lower-triangle launch and the slab reduction),
+ * 11 = one quadratic form v'Gv from the lower triangle of G with its scalar reduction (whatever the handle's read mode;
+ * BH_ERR_PRECONDITION when the width is not served) — all three BH_ERR_PRECONDITION unless the handle is in the Gram form
+ * (bh_hess_set_form); the counters of bh_hess_get_gram_read do not move.  Returns the average milliseconds per launch. */
 int32_t bh_time_kernel(bh_hess* H, int32_t kind, int32_t reps, double* avg_ms);
 /* Device self-test of the wave64 DPP/permlane reduction network (sum and NaN-propagating min). */
 int32_t bh_selftest(void);

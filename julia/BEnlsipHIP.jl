@@ -88,9 +88,16 @@ function gram_cauchy_eq!(flag::Bool = true)
     return flag
 end
 
+# How a Gram-form handle reads G (bh_hess_set_gram_read, INTEGRATION.md): 0 the full read (default), 1 products from the lower triangle,
+# 2 also vthv / the line search from G (v'Gv can come out <= 0 near zero, which ||Jv||^2 cannot).  Opt-in, only with gram_hessian!(true).
+#     BEnlsipHIP.gram_read!(1)
+const GRAM_READ = Ref(Int32(0))
+gram_read!(mode::Integer = 1) = (GRAM_READ[] = Int32(mode))
+
 function product_handle(H::BEnlsip.AlHessian{Float64})
     h = handle(H)
     GRAM_HESSIAN[] && check(ccall((:bh_hess_set_form, libbh), Int32, (Ptr{Cvoid}, Int32), h, 1), "bh_hess_set_form")   # BH_HESS_GRAM
+    GRAM_HESSIAN[] && check(ccall((:bh_hess_set_gram_read, libbh), Int32, (Ptr{Cvoid}, Int32), h, GRAM_READ[]), "bh_hess_set_gram_read")
     return h
 end
 

@@ -7,11 +7,16 @@ number of products per J.  (Not to be confused with tools/gram_timing.py, which 
 
     python tools/gn_gram_timing.py [--out FILE] [--quick]
     python tools/gn_gram_timing.py --cg-fused [--out FILE] [--one]
+    python tools/gn_gram_timing.py --gram-read [--out FILE]
 
 --cg-fused: the CG iteration on a Gram-form handle with option gram_cg_fused 0 / 1 alternated in one process (same handle, same
 subproblem): median of 5 bh_pcg_dev calls each, wall time per call / H*p products, with the min - max spread; box constraints
 at config 2, config 3 and n = 8192, and config 3 with 64 ("config-5 shape") and 8 linear equalities (A = u(4, .)).
 --one: a single pair of calls on the config-5 shape with the option on, nothing else (rocprofv3 kernel traces).
+--gram-read: the three read modes of a Gram-form handle (bh_hess_set_gram_read) at config 3 and n = 8192 (wider handles are not served): back-to-back
+bh_time_kernel kind 10 (the product the handle performs), kind 11 (one quadratic form from G) and, for comparison, kind 1 (the J v
+sweep a vthv costs); median of 5 blocks of 20 launches (min - max), with the bytes each one is specified to read.  A library built
+before the switch existed gives the "full" rows only (A/B against an older commit in one session).
 """
 import argparse
 import os
@@ -101,16 +106,59 @@ def cg_fused_mode(args):
             f.write("\n".join(LINES) + "\n")
 
 
+def gram_read_mode(args):
+    import ctypes as ct
+    lib = bh._lib.lib()
+    setter = getattr(lib, "bh_hess_set_gram_read", None)
+    if setter is not None:
+        setter.argtypes, setter.restype = [ct.c_void_p, ct.c_int32], ct.c_int32
+    say("# tools/gn_gram_timing.py --gram-read: G·v (bh_time_kernel kind 10), v'Gv from G (kind 11) and the J v sweep (kind 1) under the "
+        "read modes of bh_hess_set_gram_read, one MI355X; us per launch, median of 5 blocks of 20 back-to-back launches (min - max)")
+
+    def med(H, kind):
+        t = [1e3 * H.time_kernel(kind, reps=20) for _ in range(5)]
+        return "%.1f us (%.1f - %.1f)" % (float(np.median(t)), min(t), max(t))
+
+    for label, d, n in [("config 3", 65536, 4096), ("n = 8192", 32768, 8192)]:          # (8192 < n <= 16384 is not served)
+        ld = (n + 15) // 16 * 16
+        H = bh.AlHessian.synthetic(d, n, seed=1, colscale=bh.synthetic.column_scale(n, 1), mu=10.0)
+        H.set_form("gram")
+        full, tri = 8.0 * n * ld + 16.0 * n, 16.0 * sum(i // 2 + 1 for i in range(n)) + 16.0 * n
+        say("%s (d = %d, n = %d): J v sweep %s, %.0f bytes; full read %.0f bytes, lower triangle %.0f bytes (slab traffic not "
+            "counted)" % (label, d, n, med(H, 1), 8.0 * d * ld + 8.0 * n, full, tri))
+        for mode, name in enumerate(("full", "lower", "lower+quad")):
+            if mode and setter is None:
+                say("    (this library has no bh_hess_set_gram_read: the full read only)")
+                break
+            if setter is not None:
+                bh._lib.check(setter(H.handle, mode), "bh_hess_set_gram_read")
+            row = "    %-10s G·v %s, bytes_per_hmul %.0f" % (name, med(H, 10), H.stats()["bytes_per_hmul"])
+            if setter is not None:
+                try:
+                    row += "; v'Gv from G %s" % med(H, 11)
+                except bh.BenlsipHipError:
+                    row += "; v'Gv from G: width not served"
+            say(row)
+        H.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(LINES) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="config 2 and 3 only, no Cauchy search (rocprofv3 runs)")
     ap.add_argument("--cg-fused", action="store_true", help="option gram_cg_fused 0 / 1 alternated on Gram-form handles")
     ap.add_argument("--one", action="store_true", help="with --cg-fused: two calls on the config-5 shape with the option on, nothing else")
+    ap.add_argument("--gram-read", action="store_true", help="bh_time_kernel kinds 10, 11 and 1 under the three read modes of bh_hess_set_gram_read")
     args = ap.parse_args()
     bh.init(0)
     if args.cg_fused:
         cg_fused_mode(args)
+        return
+    if args.gram_read:
+        gram_read_mode(args)
         return
     shapes = [("config 2", 8192, 1024), ("config 3", 65536, 4096)]
     if not args.quick:
