@@ -451,6 +451,10 @@ struct bh_hess {
     int gram_read = GRAM_READ_FULL;
     int64_t products_lower = 0;    // launches of gram_symv_kernel<..., QUAD = 0> since the handle was created
     int64_t quads_from_g = 0;      // launches of gram_symv_kernel<..., QUAD = 1>
+    // which box-constrained Cauchy search the Gram form runs (bh_hess_set_cauchy_search): remembered in either form, never rebuilds G
+    int cauchy_search = BH_CAUCHY_STEPWISE;
+    int64_t searches_sorted = 0;   // searches the sorted form (bh_cauchysort.hip.h) completed; a handed-back call is not one
+    double* csort = nullptr;       // T, b, U / L parts, the scan arrays, rank, inv and the hand-back flag of the sorted form (lazy)
     // compact image of the free columns (option free_image; bh_free_image_plan.h, bh_freeimg.hip.h)
     double* Jf = nullptr;          // (d + q_eff) x fi.ldf row-major, from the image pool
     int64_t Jf_doubles = 0;        // capacity of the allocation behind Jf
@@ -2008,9 +2012,9 @@ int32_t bh_hess_set_mu(bh_hess* H, double mu) {
 static void gram_free(bh_hess* H) {
     if (H->G || H->gpart) {
         if (g_ctx.init) (void)hipStreamSynchronize(g_ctx.stream);   // launches still reading G may be queued
-        dev_free(H->G); dev_free(H->gpart); dev_free(H->geq);
+        dev_free(H->G); dev_free(H->gpart); dev_free(H->geq); dev_free(H->csort);
     }
-    H->G = nullptr; H->gpart = nullptr; H->geq = nullptr; H->geq_doubles = 0;
+    H->G = nullptr; H->gpart = nullptr; H->geq = nullptr; H->geq_doubles = 0; H->csort = nullptr;
     H->G_valid = false;
 }
 
@@ -2081,6 +2085,21 @@ int32_t bh_hess_get_gram_read(const bh_hess* H, int32_t* mode, int32_t* served, 
     return BH_OK;
 }
 
+int32_t bh_hess_set_cauchy_search(bh_hess* H, int32_t mode) {
+    if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
+    if (mode != BH_CAUCHY_STEPWISE && mode != BH_CAUCHY_SORTED) return fail(BH_ERR_INVALID_ARG, "mode is BH_CAUCHY_STEPWISE (0) or BH_CAUCHY_SORTED (1)");
+    H->cauchy_search = mode;                    // (G, the step-chain ledger and the byte counters do not depend on it)
+    return BH_OK;
+}
+
+int32_t bh_hess_get_cauchy_search(const bh_hess* H, int32_t* mode, int32_t* served, int64_t* searches_sorted) {
+    if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
+    if (mode) *mode = H->cauchy_search;
+    if (served) *served = H->n <= 16384 ? 1 : 0;
+    if (searches_sorted) *searches_sorted = H->searches_sorted;
+    return BH_OK;
+}
+
 int32_t bh_hess_free_image_info(const bh_hess* H, const bh_proj* P, int32_t* state, int64_t* width, int64_t* builds, int64_t* moves,
                                 int64_t* calls_served) {
     if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
@@ -2141,7 +2160,7 @@ int32_t bh_hess_destroy(bh_hess* H) {
     dev_free(H->fi_map); dev_free(H->fi_ops);
     dev_free(H->vpad); dev_free(H->zpad); dev_free(H->upad); dev_free(H->tbuf); dev_free(H->timg); dev_free(H->timg_gen); dev_free(H->cblk);
     dev_free(H->partials); dev_free(H->sq_partials); dev_free(H->scalar);
-    dev_free(H->G); dev_free(H->gpart); dev_free(H->geq);
+    dev_free(H->G); dev_free(H->gpart); dev_free(H->geq); dev_free(H->csort);
     for (auto e : H->ev) if (e) (void)hipEventDestroy(e);
     delete H;
     return BH_OK;
@@ -3580,7 +3599,7 @@ struct CauchyRun {
 };
 
 // Decides everything about the search from the handles and the options.  Launches and allocates nothing.
-static CauchyPlan cauchy_make_plan(const bh_hess* H, const bh_proj* P) {
+static CauchyPlan cauchy_make_plan(const bh_hess* H, const bh_proj* P, bool allow_sorted) {
     const int mA = (int)P->mA;
     CauchySelectIn in{};
     in.gram_handle = H->form == BH_HESS_GRAM; in.mA = mA; in.comm = comm_active(); in.lda_is_ld = P->ldA == H->ld;
@@ -3588,6 +3607,7 @@ static CauchyPlan cauchy_make_plan(const bh_hess* H, const bh_proj* P) {
     in.cauchy_image = g_ctx.opt_cauchy_image; in.cauchy_image_max_ma = g_ctx.opt_cauchy_image_max_ma; in.cauchy_fused = g_ctx.opt_cauchy_fused;
     in.cauchy_gram = g_ctx.opt_cauchy_gram; in.cauchy_gram_eq = g_ctx.opt_cauchy_gram_eq; in.cauchy_image_refresh = g_ctx.opt_cauchy_image_refresh;
     in.n = H->n; in.cauchy_block = g_ctx.opt_cauchy_block;
+    in.gram_sorted = allow_sorted && H->cauchy_search == BH_CAUCHY_SORTED;      // (allow_sorted = false: the re-run of a handed-back call)
     const CauchySelection sel = cauchy_select(in);
     CauchyPlan p;
     p.form = sel.form; p.fused = sel.fused; p.refresh = sel.refresh; p.block = sel.block;
@@ -3626,6 +3646,10 @@ static CauchyPlan cauchy_make_plan(const bh_hess* H, const bh_proj* P) {
     return p;
 }
 
+// Workspace of the sorted form in doubles: T, b (ld each), the per-panel parts of U and L, the three scan arrays, rank, inv (ints), flag.
+static int64_t cauchy_sort_doubles(int64_t ld) { return (2 + 2 * CS_MAX_PANELS) * ld + 3 * (ld + 16) + ld + 16; }
+static int* cauchy_sort_flag(bh_hess* H) { return reinterpret_cast<int*>(H->csort + (2 + 2 * CS_MAX_PANELS) * H->ld + 3 * (H->ld + 16)) + 2 * H->ld; }
+
 // The buffers of the chosen form, grown before the first launch: the images t_d, t_s (+ partial sums and a 16-double tail), a and B
 // of the row-space form with equalities, a and B of the Gram form with equalities.
 static int32_t cauchy_ensure_buffers(CauchyRun& r) {
@@ -3653,6 +3677,10 @@ static int32_t cauchy_ensure_buffers(CauchyRun& r) {
         H->geq_doubles = (int64_t)(1 + mA) * H->ld;
     }
     r.sbuf[0] = r.c.w; r.sbuf[1] = r.c.Hp;
+    if (r.plan.form == CAUCHY_GRAM_SORTED && !H->csort) {
+        BH_TRY(dev_alloc(&H->csort, cauchy_sort_doubles(H->ld)));
+        BH_HIP(hipMemsetAsync(cauchy_sort_flag(H), 0, sizeof(int), r.s));      // (kernel 3 leaves the flag cleared)
+    }
     if (r.plan.fused) {
         r.pp = reinterpret_cast<CauchyPass*>(r.img_scal + 8);     // 2 x 32 bytes in the 16-double tail of timg
         r.part_pp[0] = H->timg + 2 * img_cap; r.part_pp[1] = r.part_pp[0] + 2 * kCauchyFusedGrid;
@@ -3909,6 +3937,29 @@ static int32_t cauchy_launch_pass(CauchyRun& r, int index) {
     }
 }
 
+// The sorted form (bh_cauchysort.hip.h): G made current by the route launch_hmul takes, without a product; then the three launches —
+// the same for every search length.  No host round trip before the final progress word.
+static int32_t cauchy_launch_sorted(CauchyRun& r) {
+    bh_hess* H = r.H;
+    BH_TRY(hess_ready(H));
+    BH_TRY(ensure_gram(H));                                         // G rebuilt first when it is stale, on the same stream
+    const int64_t ld = H->ld;
+    CauchySortArgs sa{};
+    sa.c = r.a; sa.G = H->G; sa.ld = ld;
+    sa.npanels = (int)((ld / 2 + CS_ROW_T * CS_ROW_CPT - 1) / (CS_ROW_T * CS_ROW_CPT));
+    sa.T = H->csort; sa.b = sa.T + ld; sa.UL = sa.b + ld; sa.scan = sa.UL + 2 * CS_MAX_PANELS * ld;
+    sa.rank = reinterpret_cast<int*>(sa.scan + 3 * (ld + 16)); sa.inv = sa.rank + ld; sa.flag = cauchy_sort_flag(H);
+    const int row_groups = (int)((H->n + CS_ROW_R - 1) / CS_ROW_R);
+    const int row_grid = std::max(1, std::min(row_groups, 4 * g_ctx.n_cu / sa.npanels));
+    const int key_tiles = (int)((H->n + CS_RANK_TILE - 1) / CS_RANK_TILE);
+    BH_HIP(hipMemsetAsync(sa.rank, 0, (size_t)ld * sizeof(int), r.s));  // the tiles add their counts into it
+    hipLaunchKernelGGL(cauchy_sort_rank_kernel, dim3((unsigned)((ld + CS_RANK_T - 1) / CS_RANK_T), (unsigned)key_tiles), dim3(CS_RANK_T), 0, r.s, sa);
+    hipLaunchKernelGGL(cauchy_sort_rows_kernel, dim3((unsigned)row_grid, (unsigned)sa.npanels), dim3(CS_ROW_T), 0, r.s, sa);
+    hipLaunchKernelGGL(cauchy_sort_scan_kernel, dim3(1), dim3(CS_SCAN_T), 0, r.s, sa);
+    BH_HIP(hipGetLastError());
+    return BH_OK;
+}
+
 // Counters of the handle and the record bh_cauchy_info reads, from the plan and the final progress word.
 static void cauchy_account(CauchyRun& r, const MirrorWord& mw, uint64_t launches_in) {
     bh_hess* H = r.H; bh_proj* P = r.P;
@@ -3930,7 +3981,8 @@ static void cauchy_account(CauchyRun& r, const MirrorWord& mw, uint64_t launches
 // mA x mA Cholesky on the device.  On return lincons' active set is the one the reference would hold (fix_chunks_out).
 // Which form runs: cauchy_make_plan (the rule: bh_cauchy_plan.h); its passes: cauchy_launch_pass.
 static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double* g, const double* xlow, const double* xupp, double delta,
-                           double* s_out, uint64_t* fix_chunks_out, int32_t* n_breakpoints, int32_t* n_hmul_out, bool dev) {
+                           double* s_out, uint64_t* fix_chunks_out, int32_t* n_breakpoints, int32_t* n_hmul_out, bool dev,
+                           bool allow_sorted = true) {
     BH_REQUIRE_INIT();
     if (!H || !P) return fail(BH_ERR_INVALID_ARG, "NULL handle");
     if (!x || !g || !xlow || !xupp || !s_out) return fail(BH_ERR_INVALID_ARG, "NULL vector argument");
@@ -3964,7 +4016,7 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     a.box = (mA == 0) ? 1 : 0;
     a.mirror = c.d_mirror; a.tag = next_mirror_tag(c);
 
-    run.plan = cauchy_make_plan(H, P);
+    run.plan = cauchy_make_plan(H, P, allow_sorted);
     const CauchyPlan& plan = run.plan;
     run.img_rows = H->d + H->q_eff;
     run.img_cap = (std::max<int64_t>(H->d + H->q, 1) + 1) / 2 * 2;
@@ -3974,7 +4026,16 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     hipLaunchKernelGGL(cauchy_init_kernel, dim3(1), dim3(CG_T), 0, s, a);
     if (mA > 0) BH_TRY(launch_reduced_factor(P, true, nullptr));
     MirrorWord mw{};
-    if (plan.form == CAUCHY_GRAM) {
+    if (plan.form == CAUCHY_GRAM_SORTED) {
+        BH_TRY(cauchy_launch_sorted(run));
+        BH_TRY(wait_mirror(c, a.tag, plan.max_pass, &mw));           // published once, by the scan kernel
+        // a non-finite g, a NaN bound or a non-finite phi', phi'' at the stop: this call runs on the path the handle takes with
+        // BH_CAUCHY_STEPWISE — codes and bits are that path's; it is not counted as a sorted search
+        if (mw.status == kCauchyHandBack)
+            return cauchy_impl(H, P, x, g, xlow, xupp, delta, s_out, fix_chunks_out, n_breakpoints, n_hmul_out, dev, false);
+        H->stats.n_hmul += 1;                                        // one read of G
+        H->searches_sorted += 1;
+    } else if (plan.form == CAUCHY_GRAM) {
         const int launched = plan.max_pass, off = plan.sched.off;   // one launch stands for every pass; off = 0 (not the one-kernel row-space form)
         BH_TRY(launch_hmul(H, c.p, c.Hp, c.d_state, -1));           // Hd = H*d    :609  (rebuilds G first when it is stale)
         H->stats.n_hmul += 1;

@@ -14,6 +14,7 @@ enum CauchyForm : int {
     CAUCHY_ROWSPACE_EQ = 2,   // row space of J with linear equalities
     CAUCHY_GRAM = 3,          // Gram-form handle: the whole box-constrained search in one launch (bh_cauchygram.hip.h)
     CAUCHY_GRAM_EQ = 4,       // Gram-form handle with linear equalities (bh_cauchygrameq.hip.h)
+    CAUCHY_GRAM_SORTED = 5,   // Gram-form handle, box constraints: one sorted sweep over G (bh_hess_set_cauchy_search, bh_cauchysort.hip.h)
 };
 
 struct CauchySelectIn {
@@ -26,6 +27,7 @@ struct CauchySelectIn {
     int64_t cauchy_image, cauchy_image_max_ma, cauchy_fused, cauchy_gram, cauchy_gram_eq, cauchy_image_refresh;   // the options
     int64_t n;                    // columns of J (the blocked search keeps the whole vector side in registers: n <= 4096)
     int64_t cauchy_block;         // option cauchy_block = K: breakpoints per launch of the one-kernel row-space search (0, 1: one)
+    bool gram_sorted;             // the handle's switch bh_hess_set_cauchy_search is at BH_CAUCHY_SORTED (no option: a per-handle mode)
 };
 
 struct CauchySelection {
@@ -41,9 +43,13 @@ constexpr int64_t kCauchyBlockMaxN = 4096;
 inline CauchySelection cauchy_select(const CauchySelectIn& in) {
     const int mA = in.mA;
     CauchySelection o{CAUCHY_SWEEP, false, 0, 0};
+    // Gram-form handle, box constraints, one rank, the handle's switch at BH_CAUCHY_SORTED: init -> ranks -> row sums of G -> scan, the
+    // same three launches for every search length (bh_cauchysort.hip.h).  Ahead of "cauchy_gram" and independent of every Cauchy
+    // option; any other handle or constraint set takes the path it takes without the switch.
+    if (in.gram_sorted && in.gram_handle && mA == 0 && !in.comm) o.form = CAUCHY_GRAM_SORTED;
     // Gram-form handle, box constraints, one rank, option "cauchy_gram": init -> G d -> cauchy_gram_kernel, the whole search in one
     // launch (bh_cauchygram.hip.h).  Any other case takes the path it takes without the option.
-    if (in.cauchy_gram != 0 && in.gram_handle && mA == 0 && !in.comm) o.form = CAUCHY_GRAM;
+    else if (in.cauchy_gram != 0 && in.gram_handle && mA == 0 && !in.comm) o.form = CAUCHY_GRAM;
     // Gram-form handle, 1 <= mA <= 64, one rank, option "cauchy_gram_eq": the linear-equality form in the column space of G
     // (bh_cauchygrameq.hip.h) — a = G D g, B = G D A' from one G v launch and one GEMM over n rows, re-formed every
     // kCauchyGramEqRefresh-th pass; per pass [factor + solves: y] -> [Hd = -a - B y | d = P(-g) | t_fresh] -> [decision from Hd].

@@ -26,6 +26,7 @@
 #include "bh_cauchyblock.hip.h"
 #include "bh_cauchygram.hip.h"
 #include "bh_cauchygrameq.hip.h"
+#include "bh_cauchysort.hip.h"
 #include "bh_minor.hip.h"
 #include "bh_gngram.hip.h"
 #include "bh_gramcg.hip.h"

@@ -195,6 +195,36 @@ class AlHessian:
         """Quadratic forms v'Gv served from G since the handle was created (``bh_hess_get_gram_read``)."""
         return self._get_gram_read()[3]
 
+    _CAUCHY_SEARCHES = {"stepwise": _lib.BH_CAUCHY_STEPWISE, "sorted": _lib.BH_CAUCHY_SORTED}
+
+    def set_cauchy_search(self, mode):
+        """``bh_hess_set_cauchy_search``: which box-constrained Cauchy search the Gram form runs — "stepwise" (the default: one
+        breakpoint after the other) or "sorted" (the whole search from one sorted sweep over G, ``cauchy_info`` form 5).  Remembered
+        in either form; never rebuilds G."""
+        if mode not in self._CAUCHY_SEARCHES:
+            raise ValueError("cauchy search is 'stepwise' or 'sorted', got %r" % (mode,))
+        check(_lib.lib().bh_hess_set_cauchy_search(self._h, self._CAUCHY_SEARCHES[mode]), "bh_hess_set_cauchy_search")
+
+    def _get_cauchy_search(self):
+        m, s, c = ct.c_int32(0), ct.c_int32(0), ct.c_int64(0)
+        check(_lib.lib().bh_hess_get_cauchy_search(self._h, ct.byref(m), ct.byref(s), ct.byref(c)), "bh_hess_get_cauchy_search")
+        return m.value, s.value, c.value
+
+    @property
+    def cauchy_search(self):
+        """"stepwise" or "sorted" (``bh_hess_get_cauchy_search``)."""
+        return {v: k for k, v in self._CAUCHY_SEARCHES.items()}[self._get_cauchy_search()[0]]
+
+    @property
+    def cauchy_search_served(self):
+        """Whether the handle's width is one the sorted search serves (n <= 16384, the Gram form's own limit)."""
+        return bool(self._get_cauchy_search()[1])
+
+    @property
+    def searches_sorted(self):
+        """Searches the sorted form completed since the handle was created (a handed-back call is not one)."""
+        return self._get_cauchy_search()[2]
+
     def __mul__(self, v):
         return hmul(self, v)
 

@@ -222,6 +222,33 @@ int32_t bh_hess_get_form(const bh_hess* H, int32_t* form, int64_t* gram_builds);
 #define BH_GRAM_READ_LOWER_QUAD  2
 int32_t bh_hess_set_gram_read(bh_hess* H, int32_t mode);
 int32_t bh_hess_get_gram_read(const bh_hess* H, int32_t* mode, int32_t* served, int64_t* products_lower, int64_t* quads_from_g);
+/* Which box-constrained Cauchy search a handle in the Gram form runs.  Opt-in per handle, next to bh_hess_set_gram_read; no option key.
+ *   BH_CAUCHY_STEPWISE  the default: every path, launch, counter and bit is what it is without this switch.
+ *   BH_CAUCHY_SORTED    bh_cauchy_step(_dev) on a Gram-form handle, no linear equalities, one rank: the search from ONE sorted sweep over
+ *                       G (bh_cauchy_info form 5).  With box constraints d_i = -g_i while variable i is free, so every breakpoint time
+ *                       T_i = b_i / d_i is known before the first pass and the variables are fixed in the order of (T_i, i); phi' and
+ *                       phi'' of every segment follow from one read of the free rows of G plus prefix and true suffix sums.  Three
+ *                       launches behind the initial one (cauchy_sort_rank_kernel, cauchy_sort_rows_kernel, cauchy_sort_scan_kernel),
+ *                       the same for every search length; no host round trip before the final progress word.  It goes ahead of option
+ *                       "cauchy_gram" and is independent of every Cauchy option.  *n_hmul of bh_cauchy_step(_dev) is the number of
+ *                       decisions k* + 1 (the reference's H*d products, as in every other form), n_breakpoints = k*; stats.n_hmul
+ *                       grows by 1 (one read of G), stats.n_jv by nothing.  The step agrees with the other forms to rounding (same
+ *                       active set, same counts; bit for bit on exactly representable data); a repeated search is bit-identical.
+ *                       BH_GRAM_READ_LOWER does not apply: the form reads whole contiguous rows, like forms 3 and 4.
+ *                       Any other handle or constraint set (implicit form, linear equalities, several ranks) takes the path it takes
+ *                       without the switch, silently and bit for bit.
+ *                       Hand-back: a non-finite g or a NaN bound on a free variable, or a non-finite phi' or phi'' at the stop, makes
+ *                       the library run that call again on the path the handle takes with BH_CAUCHY_STEPWISE — return codes and
+ *                       bits are that path's; searches_sorted does not count such a call.  "No breakpoint left" is decided by the
+ *                       same rule as in the other forms and returns the same BH_ERR_PRECONDITION.
+ * bh_hess_set_cauchy_search may be called in either form: the mode is remembered and takes effect while the handle is in the Gram form.
+ * It never rebuilds G and raises no event on the step-chain notes.  NULL handle or a mode outside 0..1: BH_ERR_INVALID_ARG, the
+ * handle keeps its mode.  bh_hess_get_cauchy_search: the mode; served = 1 for n <= 16384 (the Gram form's own limit);
+ * searches_sorted = searches the sorted form completed since the handle was created.  Any pointer may be NULL. */
+#define BH_CAUCHY_STEPWISE 0
+#define BH_CAUCHY_SORTED   1
+int32_t bh_hess_set_cauchy_search(bh_hess* H, int32_t mode);
+int32_t bh_hess_get_cauchy_search(const bh_hess* H, int32_t* mode, int32_t* served, int64_t* searches_sorted);
 int32_t bh_hess_shape(const bh_hess* H, int64_t* d, int64_t* n, int64_t* q);
 /* The compact image of the free columns (option "free_image"): one row per row of the image of J, only the columns of the
  * variables that are free, dense; the box-constrained CG loop of bh_pcg* streams it instead of J.
@@ -329,6 +356,7 @@ int32_t bh_cauchy_step(bh_hess* H, bh_proj* P, const double* x, const double* g,
 /* Form and launch count of the last bh_cauchy_step(_dev) on this bh_proj:
  *   form 0 = one H*d per breakpoint, 1 = row space of J (box), 2 = row space of J with equalities, 3 = from G in one launch,
  *   form 4 = from G with linear equalities (option "cauchy_gram_eq")
+ *   form 5 = from G in one sorted sweep (bh_hess_set_cauchy_search at BH_CAUCHY_SORTED): the same few launches for every search length
  *   n_launches = kernels enqueued by that call (over-launched prologue-only passes included).
  * BH_ERR_PRECONDITION before the first search on the handle. */
 int32_t bh_cauchy_info(const bh_proj* P, int32_t* form, int32_t* n_launches);
