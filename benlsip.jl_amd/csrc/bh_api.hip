@@ -3,6 +3,7 @@
 // exports return once the host has what it is owed (option final_sync).
 #include "../../include/benlsip_hip.h"
 #include "bh_cauchy_plan.h"
+#include "bh_cauchy_rows_plan.h"
 #include "bh_free_image_plan.h"
 #include "bh_gram_ingest_plan.h"
 #include "bh_kernels.hip.h"
@@ -455,6 +456,11 @@ struct bh_hess {
     int cauchy_search = BH_CAUCHY_STEPWISE;
     int64_t searches_sorted = 0;   // searches the sorted form (bh_cauchysort.hip.h) completed; a handed-back call is not one
     double* csort = nullptr;       // T, b, U / L parts, the scan arrays, rank, inv and the hand-back flag of the sorted form (lazy)
+    // which box-constrained Cauchy search the implicit form runs (bh_hess_set_cauchy_rows): remembered in either form, rebuilds nothing
+    int cauchy_rows = BH_CAUCHY_ROWS_STEPWISE;
+    int64_t searches_rows_sorted = 0;   // searches the sorted rows form (bh_cauchyrowsort.hip.h) completed; a handed-back call is not one
+    double* crows = nullptr;       // T, b, phi'' / X, the scan array, rank, inv, the hand-back flag and the slabs of that form (lazy)
+    int crows_grid = 0;            // slabs crows holds: the grid of cauchy_rowsort_rows_kernel on this handle
     // compact image of the free columns (option free_image; bh_free_image_plan.h, bh_freeimg.hip.h)
     double* Jf = nullptr;          // (d + q_eff) x fi.ldf row-major, from the image pool
     int64_t Jf_doubles = 0;        // capacity of the allocation behind Jf
@@ -2100,6 +2106,22 @@ int32_t bh_hess_get_cauchy_search(const bh_hess* H, int32_t* mode, int32_t* serv
     return BH_OK;
 }
 
+int32_t bh_hess_set_cauchy_rows(bh_hess* H, int32_t mode) {
+    if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
+    if (mode != BH_CAUCHY_ROWS_STEPWISE && mode != BH_CAUCHY_ROWS_SORTED)
+        return fail(BH_ERR_INVALID_ARG, "mode is BH_CAUCHY_ROWS_STEPWISE (0) or BH_CAUCHY_ROWS_SORTED (1)");
+    H->cauchy_rows = mode;                      // (J, G, the step-chain ledger and the byte counters do not depend on it)
+    return BH_OK;
+}
+
+int32_t bh_hess_get_cauchy_rows(const bh_hess* H, int32_t* mode, int32_t* served, int64_t* searches_rows_sorted) {
+    if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
+    if (mode) *mode = H->cauchy_rows;
+    if (served) *served = cauchy_rows_served(H->n, H->ld) ? 1 : 0;
+    if (searches_rows_sorted) *searches_rows_sorted = H->searches_rows_sorted;
+    return BH_OK;
+}
+
 int32_t bh_hess_free_image_info(const bh_hess* H, const bh_proj* P, int32_t* state, int64_t* width, int64_t* builds, int64_t* moves,
                                 int64_t* calls_served) {
     if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
@@ -2160,7 +2182,7 @@ int32_t bh_hess_destroy(bh_hess* H) {
     dev_free(H->fi_map); dev_free(H->fi_ops);
     dev_free(H->vpad); dev_free(H->zpad); dev_free(H->upad); dev_free(H->tbuf); dev_free(H->timg); dev_free(H->timg_gen); dev_free(H->cblk);
     dev_free(H->partials); dev_free(H->sq_partials); dev_free(H->scalar);
-    dev_free(H->G); dev_free(H->gpart); dev_free(H->geq); dev_free(H->csort);
+    dev_free(H->G); dev_free(H->gpart); dev_free(H->geq); dev_free(H->csort); dev_free(H->crows);
     for (auto e : H->ev) if (e) (void)hipEventDestroy(e);
     delete H;
     return BH_OK;
@@ -3608,7 +3630,10 @@ static CauchyPlan cauchy_make_plan(const bh_hess* H, const bh_proj* P, bool allo
     in.cauchy_gram = g_ctx.opt_cauchy_gram; in.cauchy_gram_eq = g_ctx.opt_cauchy_gram_eq; in.cauchy_image_refresh = g_ctx.opt_cauchy_image_refresh;
     in.n = H->n; in.cauchy_block = g_ctx.opt_cauchy_block;
     in.gram_sorted = allow_sorted && H->cauchy_search == BH_CAUCHY_SORTED;      // (allow_sorted = false: the re-run of a handed-back call)
-    const CauchySelection sel = cauchy_select(in);
+    CauchyRowsIn rin{};
+    rin.rows_sorted = allow_sorted && H->cauchy_rows == BH_CAUCHY_ROWS_SORTED;
+    rin.gram_handle = in.gram_handle; rin.mA = mA; rin.comm = in.comm; rin.n = H->n; rin.ld = H->ld;
+    const CauchySelection sel = cauchy_rows_apply(rin, cauchy_select(in));      // (bh_cauchy_rows_plan.h: form 6 or the selection as it is)
     CauchyPlan p;
     p.form = sel.form; p.fused = sel.fused; p.refresh = sel.refresh; p.block = sel.block;
     // B = J~ D A' (rows x mA): ONE sweep on the matrix cores (image_b_mfma_kernel) when the images share their leading dimension,
@@ -3649,6 +3674,34 @@ static CauchyPlan cauchy_make_plan(const bh_hess* H, const bh_proj* P, bool allo
 // Workspace of the sorted form in doubles: T, b (ld each), the per-panel parts of U and L, the three scan arrays, rank, inv (ints), flag.
 static int64_t cauchy_sort_doubles(int64_t ld) { return (2 + 2 * CS_MAX_PANELS) * ld + 3 * (ld + 16) + ld + 16; }
 static int* cauchy_sort_flag(bh_hess* H) { return reinterpret_cast<int*>(H->csort + (2 + 2 * CS_MAX_PANELS) * H->ld + 3 * (H->ld + 16)) + 2 * H->ld; }
+
+// Workspace of the sorted rows form in doubles: T, b (ld each), phi'' and X (ld each), the scan array, rank, inv (ints), flag; then
+// one slab of 2 ld doubles per workgroup of the row scan.
+static int64_t cauchy_rows_head_doubles(int64_t ld) { return 4 * ld + (ld + 16) + ld + 16; }
+static int* cauchy_rows_flag(bh_hess* H) { return reinterpret_cast<int*>(H->crows + 4 * H->ld + (H->ld + 16)) + 2 * H->ld; }
+static int cauchy_rows_grid(const bh_hess* H, int64_t img_rows) {
+    const int64_t groups = (img_rows + RS_R - 1) / RS_R;
+    return (int)std::max<int64_t>(1, std::min<int64_t>(groups, (int64_t)RS_GRID_PER_CU * g_ctx.n_cu));
+}
+// Allocated at the first search that wants it; false (and no error left behind) when the device has no room: that call and every
+// later one stay on the stepwise path until an allocation succeeds.
+static bool cauchy_rows_workspace(bh_hess* H, hipStream_t s) {
+    if (H->crows) return true;
+    const int grid = cauchy_rows_grid(H, H->d + H->q);
+    void* p = nullptr;
+    if (hipMalloc(&p, (size_t)(cauchy_rows_head_doubles(H->ld) + (int64_t)grid * 2 * H->ld) * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    H->crows = static_cast<double*>(p); H->crows_grid = grid;
+    if (hipMemsetAsync(cauchy_rows_flag(H), 0, sizeof(int), s) != hipSuccess) {      // (the scan kernel leaves the flag cleared)
+        (void)hipGetLastError();
+        dev_free(H->crows);
+        H->crows = nullptr; H->crows_grid = 0;
+        return false;
+    }
+    return true;
+}
 
 // The buffers of the chosen form, grown before the first launch: the images t_d, t_s (+ partial sums and a 16-double tail), a and B
 // of the row-space form with equalities, a and B of the Gram form with equalities.
@@ -3960,6 +4013,30 @@ static int32_t cauchy_launch_sorted(CauchyRun& r) {
     return BH_OK;
 }
 
+// The sorted rows form (bh_cauchyrowsort.hip.h): ranks, the one read of J, the slab sums, the scan — the same launches for every
+// search length.  No host round trip before the final progress word.
+static int32_t cauchy_launch_rows_sorted(CauchyRun& r) {
+    bh_hess* H = r.H;
+    BH_TRY(hess_ready(H));
+    const int64_t ld = H->ld;
+    CauchyRowSortArgs ra{};
+    CauchySortArgs& sa = ra.s;
+    sa.c = r.a; sa.G = nullptr; sa.ld = ld; sa.UL = nullptr; sa.npanels = 0;
+    sa.T = H->crows; sa.b = sa.T + ld; ra.red = sa.b + ld; sa.scan = ra.red + 2 * ld;
+    sa.rank = reinterpret_cast<int*>(sa.scan + (ld + 16)); sa.inv = sa.rank + ld; sa.flag = cauchy_rows_flag(H);
+    ra.slab = H->crows + cauchy_rows_head_doubles(ld);
+    ra.J = H->Jd; ra.nrows = r.img_rows; ra.d_rows = H->d; ra.mu = H->mu;
+    ra.grid = std::min(cauchy_rows_grid(H, r.img_rows), H->crows_grid);
+    const int key_tiles = (int)((H->n + CS_RANK_TILE - 1) / CS_RANK_TILE);
+    BH_HIP(hipMemsetAsync(sa.rank, 0, (size_t)ld * sizeof(int), r.s));  // the tiles add their counts into it
+    hipLaunchKernelGGL(cauchy_sort_rank_kernel, dim3((unsigned)((ld + CS_RANK_T - 1) / CS_RANK_T), (unsigned)key_tiles), dim3(CS_RANK_T), 0, r.s, sa);
+    hipLaunchKernelGGL(cauchy_rowsort_rows_kernel, dim3((unsigned)ra.grid), dim3(RS_T), 0, r.s, ra);
+    hipLaunchKernelGGL(cauchy_rowsort_reduce_kernel, dim3((unsigned)((ld + RS_RED_T - 1) / RS_RED_T), 2u), dim3(RS_RED_T), 0, r.s, ra);
+    hipLaunchKernelGGL(cauchy_rowsort_scan_kernel, dim3(1), dim3(CS_SCAN_T), 0, r.s, ra);
+    BH_HIP(hipGetLastError());
+    return BH_OK;
+}
+
 // Counters of the handle and the record bh_cauchy_info reads, from the plan and the final progress word.
 static void cauchy_account(CauchyRun& r, const MirrorWord& mw, uint64_t launches_in) {
     bh_hess* H = r.H; bh_proj* P = r.P;
@@ -4017,6 +4094,8 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     a.mirror = c.d_mirror; a.tag = next_mirror_tag(c);
 
     run.plan = cauchy_make_plan(H, P, allow_sorted);
+    // (no room for the workspace of the sorted rows form: the stepwise path, without an error)
+    if (run.plan.form == CAUCHY_ROWS_SORTED && !cauchy_rows_workspace(H, s)) run.plan = cauchy_make_plan(H, P, false);
     const CauchyPlan& plan = run.plan;
     run.img_rows = H->d + H->q_eff;
     run.img_cap = (std::max<int64_t>(H->d + H->q, 1) + 1) / 2 * 2;
@@ -4035,6 +4114,14 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
             return cauchy_impl(H, P, x, g, xlow, xupp, delta, s_out, fix_chunks_out, n_breakpoints, n_hmul_out, dev, false);
         H->stats.n_hmul += 1;                                        // one read of G
         H->searches_sorted += 1;
+    } else if (plan.form == CAUCHY_ROWS_SORTED) {
+        BH_TRY(cauchy_launch_rows_sorted(run));
+        BH_TRY(wait_mirror(c, a.tag, plan.max_pass, &mw));           // published once, by the scan kernel
+        // hand-back as in form 5: this call runs on the stepwise path with both sorted forms off — codes and bits are that path's
+        if (mw.status == kCauchyHandBack)
+            return cauchy_impl(H, P, x, g, xlow, xupp, delta, s_out, fix_chunks_out, n_breakpoints, n_hmul_out, dev, false);
+        H->stats.n_jv += 1;                                          // one read of J
+        H->searches_rows_sorted += 1;
     } else if (plan.form == CAUCHY_GRAM) {
         const int launched = plan.max_pass, off = plan.sched.off;   // one launch stands for every pass; off = 0 (not the one-kernel row-space form)
         BH_TRY(launch_hmul(H, c.p, c.Hp, c.d_state, -1));           // Hd = H*d    :609  (rebuilds G first when it is stale)

@@ -15,6 +15,7 @@ enum CauchyForm : int {
     CAUCHY_GRAM = 3,          // Gram-form handle: the whole box-constrained search in one launch (bh_cauchygram.hip.h)
     CAUCHY_GRAM_EQ = 4,       // Gram-form handle with linear equalities (bh_cauchygrameq.hip.h)
     CAUCHY_GRAM_SORTED = 5,   // Gram-form handle, box constraints: one sorted sweep over G (bh_hess_set_cauchy_search, bh_cauchysort.hip.h)
+    CAUCHY_ROWS_SORTED = 6,   // implicit handle, box constraints: one sorted sweep over J (bh_hess_set_cauchy_rows, bh_cauchy_rows_plan.h)
 };
 
 struct CauchySelectIn {

@@ -27,6 +27,7 @@
 #include "bh_cauchygram.hip.h"
 #include "bh_cauchygrameq.hip.h"
 #include "bh_cauchysort.hip.h"
+#include "bh_cauchyrowsort.hip.h"
 #include "bh_minor.hip.h"
 #include "bh_gngram.hip.h"
 #include "bh_gramcg.hip.h"

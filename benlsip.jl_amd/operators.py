@@ -225,6 +225,36 @@ class AlHessian:
         """Searches the sorted form completed since the handle was created (a handed-back call is not one)."""
         return self._get_cauchy_search()[2]
 
+    _CAUCHY_ROWS = {"stepwise": _lib.BH_CAUCHY_ROWS_STEPWISE, "sorted": _lib.BH_CAUCHY_ROWS_SORTED}
+
+    def set_cauchy_rows(self, mode):
+        """``bh_hess_set_cauchy_rows``: which box-constrained Cauchy search the implicit form runs — "stepwise" (the default: one
+        breakpoint after the other) or "sorted" (the whole search from one sorted sweep over J, ``cauchy_info`` form 6).  Remembered
+        in either form; rebuilds nothing."""
+        if mode not in self._CAUCHY_ROWS:
+            raise ValueError("cauchy rows is 'stepwise' or 'sorted', got %r" % (mode,))
+        check(_lib.lib().bh_hess_set_cauchy_rows(self._h, self._CAUCHY_ROWS[mode]), "bh_hess_set_cauchy_rows")
+
+    def _get_cauchy_rows(self):
+        m, s, c = ct.c_int32(0), ct.c_int32(0), ct.c_int64(0)
+        check(_lib.lib().bh_hess_get_cauchy_rows(self._h, ct.byref(m), ct.byref(s), ct.byref(c)), "bh_hess_get_cauchy_rows")
+        return m.value, s.value, c.value
+
+    @property
+    def cauchy_rows(self):
+        """"stepwise" or "sorted" (``bh_hess_get_cauchy_rows``)."""
+        return {v: k for k, v in self._CAUCHY_ROWS.items()}[self._get_cauchy_rows()[0]]
+
+    @property
+    def cauchy_rows_served(self):
+        """Whether the handle's width is one the sorted rows search serves (n <= 4096)."""
+        return bool(self._get_cauchy_rows()[1])
+
+    @property
+    def searches_rows_sorted(self):
+        """Searches the sorted rows form completed since the handle was created (a handed-back call is not one)."""
+        return self._get_cauchy_rows()[2]
+
     def __mul__(self, v):
         return hmul(self, v)
 
@@ -550,7 +580,8 @@ def cauchy_step(x, g, H, lincons, delta, full_output=False):
 def cauchy_info(lincons):
     """``bh_cauchy_info``: ``(form, n_launches)`` of the last ``cauchy_step`` on ``lincons`` — form 0 = one ``H*d`` per breakpoint,
     1 = row space of ``J`` (box), 2 = row space of ``J`` with equalities, 3 = from ``G`` in one launch (option ``cauchy_gram``),
-    4 = from ``G`` with linear equalities (option ``cauchy_gram_eq``)."""
+    4 = from ``G`` with linear equalities (option ``cauchy_gram_eq``), 5 = from ``G`` in one sorted sweep (``set_cauchy_search``),
+    6 = from ``J`` in one sorted sweep (``set_cauchy_rows``)."""
     form, nl = ct.c_int32(-1), ct.c_int32(0)
     check(_lib.lib().bh_cauchy_info(lincons._h, ct.byref(form), ct.byref(nl)), "bh_cauchy_info")
     return form.value, nl.value

@@ -249,6 +249,38 @@ int32_t bh_hess_get_gram_read(const bh_hess* H, int32_t* mode, int32_t* served, 
 #define BH_CAUCHY_SORTED   1
 int32_t bh_hess_set_cauchy_search(bh_hess* H, int32_t mode);
 int32_t bh_hess_get_cauchy_search(const bh_hess* H, int32_t* mode, int32_t* served, int64_t* searches_sorted);
+/* Which box-constrained Cauchy search a handle in the IMPLICIT form runs.  Opt-in per handle, next to bh_hess_set_cauchy_search (whose
+ * contract is unchanged: it concerns the Gram form only); no option key.
+ *   BH_CAUCHY_ROWS_STEPWISE  the default: every path, launch, counter and bit is what it is without this switch.
+ *   BH_CAUCHY_ROWS_SORTED    bh_cauchy_step(_dev) on an implicit handle, no linear equalities, one rank, a served width: the search
+ *                       from ONE sorted sweep over J (bh_cauchy_info form 6).  The order (T_i, i) in which variables are fixed is
+ *                       known before the first pass; per row of the image [J; C] the entries of the free variables are taken in
+ *                       that order, J~ d of every segment is a true suffix sum and the part of J~ s_c already at its bounds a
+ *                       prefix sum, and phi'' = sum w S^2, s_c'Hd = sum w P S + T phi'' of every segment follow from one read of J.
+ *                       Four launches behind the initial one (cauchy_sort_rank_kernel, cauchy_rowsort_rows_kernel,
+ *                       cauchy_rowsort_reduce_kernel, cauchy_rowsort_scan_kernel), the same for every search length; no host round
+ *                       trip before the final progress word.  It goes ahead of, and is independent of, every Cauchy option
+ *                       ("cauchy_image", "cauchy_fused", "cauchy_block", "cauchy_image_refresh").  *n_hmul of bh_cauchy_step(_dev) is
+ *                       the number of decisions k* + 1 (the reference's H*d products), n_breakpoints = k*; stats.n_jv grows by 1
+ *                       (one read of J), stats.n_hmul by nothing.  The step agrees with the other forms to rounding (same active
+ *                       set, same counts; bit for bit on exactly representable data); a repeated search is bit-identical; the bits
+ *                       may depend on the number of compute units (which rows share a partial sum), as those of H*p do.
+ *                       Any other handle or constraint set (Gram form, linear equalities, several ranks, an unserved width) takes
+ *                       the path it takes without the switch, silently and bit for bit; so does a call for whose workspace the
+ *                       device has no room.
+ *                       Hand-back: as with BH_CAUCHY_SORTED — a non-finite g or a NaN bound on a free variable, or a non-finite
+ *                       phi' or phi'' at the stop, makes the library run that call again on the stepwise path with both sorted
+ *                       forms off; return codes and bits are that path's; searches_rows_sorted does not count such a call.  "No
+ *                       breakpoint left" is decided by the same rule as in the other forms and returns the same BH_ERR_PRECONDITION.
+ * The mode is remembered across bh_hess_set_form and takes effect while the handle is in the implicit form.  It never rebuilds
+ * anything and raises no event on the step-chain notes.  NULL handle or a mode outside 0..1: BH_ERR_INVALID_ARG, the handle keeps its
+ * mode.  bh_hess_get_cauchy_rows: the mode; served = 1 for n <= 4096 (the one geometry of the row scan: 512 threads x 8 ranks, a
+ * row of the image in LDS), else 0; searches_rows_sorted = searches the form completed since the handle was created.  Any pointer may
+ * be NULL. */
+#define BH_CAUCHY_ROWS_STEPWISE 0
+#define BH_CAUCHY_ROWS_SORTED   1
+int32_t bh_hess_set_cauchy_rows(bh_hess* H, int32_t mode);
+int32_t bh_hess_get_cauchy_rows(const bh_hess* H, int32_t* mode, int32_t* served, int64_t* searches_rows_sorted);
 int32_t bh_hess_shape(const bh_hess* H, int64_t* d, int64_t* n, int64_t* q);
 /* The compact image of the free columns (option "free_image"): one row per row of the image of J, only the columns of the
  * variables that are free, dense; the box-constrained CG loop of bh_pcg* streams it instead of J.
@@ -357,6 +389,7 @@ int32_t bh_cauchy_step(bh_hess* H, bh_proj* P, const double* x, const double* g,
  *   form 0 = one H*d per breakpoint, 1 = row space of J (box), 2 = row space of J with equalities, 3 = from G in one launch,
  *   form 4 = from G with linear equalities (option "cauchy_gram_eq")
  *   form 5 = from G in one sorted sweep (bh_hess_set_cauchy_search at BH_CAUCHY_SORTED): the same few launches for every search length
+ *   form 6 = from J in one sorted sweep (bh_hess_set_cauchy_rows at BH_CAUCHY_ROWS_SORTED): the same few launches for every search length
  *   n_launches = kernels enqueued by that call (over-launched prologue-only passes included).
  * BH_ERR_PRECONDITION before the first search on the handle. */
 int32_t bh_cauchy_info(const bh_proj* P, int32_t* form, int32_t* n_launches);
