@@ -23,7 +23,7 @@ BH_UNIQUE_ID_BYTES = 128
 EXPORTS = [
     "bh_init", "bh_shutdown", "bh_set_stream", "bh_synchronize", "bh_strerror", "bh_last_error_detail", "bh_device_info",
     "bh_comm_unique_id", "bh_comm_init", "bh_comm_destroy", "bh_comm_info",
-    "bh_hess_create", "bh_hess_create_async", "bh_hess_wait", "bh_hess_create_dev", "bh_hess_create_synthetic", "bh_hess_set_mu", "bh_hess_set_form", "bh_hess_get_form", "bh_hess_set_gram_read", "bh_hess_get_gram_read", "bh_hess_set_cauchy_search", "bh_hess_get_cauchy_search", "bh_hess_set_cauchy_rows", "bh_hess_get_cauchy_rows", "bh_hess_destroy", "bh_hess_shape",
+    "bh_hess_create", "bh_hess_create_async", "bh_hess_wait", "bh_hess_create_dev", "bh_hess_create_synthetic", "bh_hess_set_mu", "bh_hess_set_form", "bh_hess_get_form", "bh_hess_set_gram_read", "bh_hess_get_gram_read", "bh_hess_set_cauchy_search", "bh_hess_get_cauchy_search", "bh_hess_set_cauchy_rows", "bh_hess_get_cauchy_rows", "bh_hess_set_cauchy_rows_ranks", "bh_hess_get_cauchy_rows_ranks", "bh_hess_destroy", "bh_hess_shape",
     "bh_hess_free_image_info", "bh_hess_free_image_read",
     "bh_hmul", "bh_vthv", "bh_jv", "bh_jtv", "bh_hmul_dev", "bh_jv_dev", "bh_jtv_dev",
     "bh_proj_create", "bh_proj_set_active", "bh_proj_destroy", "bh_proj_shape", "bh_project", "bh_project_dev",
@@ -80,6 +80,8 @@ _PROTOS = {
     "bh_hess_get_cauchy_search": ([_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64)], _i32),
     "bh_hess_set_cauchy_rows": ([_vp, _i32], _i32),
     "bh_hess_get_cauchy_rows": ([_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64)], _i32),
+    "bh_hess_set_cauchy_rows_ranks": ([_vp, _i32], _i32),
+    "bh_hess_get_cauchy_rows_ranks": ([_vp, C.POINTER(_i32)], _i32),
     "bh_hess_free_image_info": ([_vp, _vp, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)], _i32),
     "bh_hess_free_image_read": ([_vp, _vp, _i64, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64)], _i32),
     "bh_hess_destroy": ([_vp], _i32),

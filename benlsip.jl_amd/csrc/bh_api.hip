@@ -458,7 +458,8 @@ struct bh_hess {
     double* csort = nullptr;       // T, b, U / L parts, the scan arrays, rank, inv and the hand-back flag of the sorted form (lazy)
     // which box-constrained Cauchy search the implicit form runs (bh_hess_set_cauchy_rows): remembered in either form, rebuilds nothing
     int cauchy_rows = BH_CAUCHY_ROWS_STEPWISE;
-    int64_t searches_rows_sorted = 0;   // searches the sorted rows form (bh_cauchyrowsort.hip.h) completed; a handed-back call is not one
+    int cauchy_rows_ranks = 0;     // bh_hess_set_cauchy_rows_ranks: that form also with a communicator, phi'' and X summed in one all-reduce
+    int64_t searches_rows_sorted = 0;  // searches the sorted rows form (bh_cauchyrowsort.hip.h) completed; a handed-back call is not one
     double* crows = nullptr;       // T, b, phi'' / X, the scan array, rank, inv, the hand-back flag and the slabs of that form (lazy)
     int crows_grid = 0;            // slabs crows holds: the grid of cauchy_rowsort_rows_kernel on this handle
     // compact image of the free columns (option free_image; bh_free_image_plan.h, bh_freeimg.hip.h)
@@ -2122,6 +2123,25 @@ int32_t bh_hess_get_cauchy_rows(const bh_hess* H, int32_t* mode, int32_t* served
     return BH_OK;
 }
 
+static bool cauchy_rows_workspace(bh_hess* H, hipStream_t s);
+
+// With a communicator the workspace of the sorted rows form is allocated HERE, not at the first search: every rank learns at the same
+// call whether it can take part, and no rank finds out alone, in the middle of a search, that it has to fall back.
+int32_t bh_hess_set_cauchy_rows_ranks(bh_hess* H, int32_t on) {
+    if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
+    if (on != 0 && on != 1) return fail(BH_ERR_INVALID_ARG, "on is 0 or 1");
+    if (on == 1 && cauchy_rows_served(H->n, H->ld) && !cauchy_rows_workspace(H, g_ctx.stream))
+        return fail(BH_ERR_HIP, "bh_hess_set_cauchy_rows_ranks: no room for the workspace of the sorted rows form");
+    H->cauchy_rows_ranks = on;                  // (J, G, the step-chain ledger and the byte counters do not depend on it)
+    return BH_OK;
+}
+
+int32_t bh_hess_get_cauchy_rows_ranks(const bh_hess* H, int32_t* on) {
+    if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
+    if (on) *on = H->cauchy_rows_ranks;
+    return BH_OK;
+}
+
 int32_t bh_hess_free_image_info(const bh_hess* H, const bh_proj* P, int32_t* state, int64_t* width, int64_t* builds, int64_t* moves,
                                 int64_t* calls_served) {
     if (!H) return fail(BH_ERR_INVALID_ARG, "NULL bh_hess");
@@ -3633,6 +3653,7 @@ static CauchyPlan cauchy_make_plan(const bh_hess* H, const bh_proj* P, bool allo
     CauchyRowsIn rin{};
     rin.rows_sorted = allow_sorted && H->cauchy_rows == BH_CAUCHY_ROWS_SORTED;
     rin.gram_handle = in.gram_handle; rin.mA = mA; rin.comm = in.comm; rin.n = H->n; rin.ld = H->ld;
+    rin.ranks = H->cauchy_rows_ranks != 0;                                      // (bh_hess_set_cauchy_rows_ranks: form 6 also with a communicator)
     const CauchySelection sel = cauchy_rows_apply(rin, cauchy_select(in));      // (bh_cauchy_rows_plan.h: form 6 or the selection as it is)
     CauchyPlan p;
     p.form = sel.form; p.fused = sel.fused; p.refresh = sel.refresh; p.block = sel.block;
@@ -4015,6 +4036,12 @@ static int32_t cauchy_launch_sorted(CauchyRun& r) {
 
 // The sorted rows form (bh_cauchyrowsort.hip.h): ranks, the one read of J, the slab sums, the scan — the same launches for every
 // search length.  No host round trip before the final progress word.
+// With a communicator (bh_hess_set_cauchy_rows_ranks) every rank scans its own img_rows = d + q_eff rows (the rows of C on rank 0
+// only), and phi'', X — plain sums over the rows — are summed over the ranks by ONE all-reduce of 2 ld doubles between the slab sums
+// and the scan: rank 0's value first, then += rank r, the same bits everywhere.  Everything else the scan reads (T, rank, g, the
+// bounds, the flag of cauchy_init_kernel) is replicated, so the replicas decide alike and a hand-back is collective; a NaN in one
+// rank's rows reaches every rank through the sum.  A rank without rows launches the row scan with a grid of 1 and no row group: one
+// slab of +0.  The exchange is not gated by the loop state: every rank always takes part.
 static int32_t cauchy_launch_rows_sorted(CauchyRun& r) {
     bh_hess* H = r.H;
     BH_TRY(hess_ready(H));
@@ -4032,6 +4059,10 @@ static int32_t cauchy_launch_rows_sorted(CauchyRun& r) {
     hipLaunchKernelGGL(cauchy_sort_rank_kernel, dim3((unsigned)((ld + CS_RANK_T - 1) / CS_RANK_T), (unsigned)key_tiles), dim3(CS_RANK_T), 0, r.s, sa);
     hipLaunchKernelGGL(cauchy_rowsort_rows_kernel, dim3((unsigned)ra.grid), dim3(RS_T), 0, r.s, ra);
     hipLaunchKernelGGL(cauchy_rowsort_reduce_kernel, dim3((unsigned)((ld + RS_RED_T - 1) / RS_RED_T), 2u), dim3(RS_RED_T), 0, r.s, ra);
+    if (comm_active()) {
+        BH_HIP(hipGetLastError());
+        BH_TRY(allreduce_inplace(ra.red, 2 * ld, H));                   // phi'', then X, by segment: the one collective of the search
+    }
     hipLaunchKernelGGL(cauchy_rowsort_scan_kernel, dim3(1), dim3(CS_SCAN_T), 0, r.s, ra);
     BH_HIP(hipGetLastError());
     return BH_OK;
@@ -4094,8 +4125,12 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     a.mirror = c.d_mirror; a.tag = next_mirror_tag(c);
 
     run.plan = cauchy_make_plan(H, P, allow_sorted);
-    // (no room for the workspace of the sorted rows form: the stepwise path, without an error)
-    if (run.plan.form == CAUCHY_ROWS_SORTED && !cauchy_rows_workspace(H, s)) run.plan = cauchy_make_plan(H, P, false);
+    // (no room for the workspace of the sorted rows form: the stepwise path, without an error — on one rank.  With a communicator
+    // the other ranks would go on into the exchange alone: an error, which bh_hess_set_cauchy_rows_ranks has normally raised already)
+    if (run.plan.form == CAUCHY_ROWS_SORTED && !cauchy_rows_workspace(H, s)) {
+        if (comm_active()) return fail(BH_ERR_HIP, "cauchy_step: no room for the workspace of the sorted rows form on this rank");
+        run.plan = cauchy_make_plan(H, P, false);
+    }
     const CauchyPlan& plan = run.plan;
     run.img_rows = H->d + H->q_eff;
     run.img_cap = (std::max<int64_t>(H->d + H->q, 1) + 1) / 2 * 2;
@@ -4117,7 +4152,12 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     } else if (plan.form == CAUCHY_ROWS_SORTED) {
         BH_TRY(cauchy_launch_rows_sorted(run));
         BH_TRY(wait_mirror(c, a.tag, plan.max_pass, &mw));           // published once, by the scan kernel
-        // hand-back as in form 5: this call runs on the stepwise path with both sorted forms off — codes and bits are that path's
+        // An exchange that timed out delivers NaN in the segments of the workgroups that gave up: behind the stop they go unseen, at
+        // or before it they look like a hand-back.  Either way the call is BH_ERR_RCCL before a counter moves — not a completed
+        // search, and not a stepwise re-run on a dead transport.  (The scan kernel runs behind the exchange: the word is final.)
+        if (comm_active()) BH_TRY(check_peer_error());
+        // hand-back as in form 5: this call runs on the stepwise path with both sorted forms off — codes and bits are that path's.
+        // With a communicator every cause is replicated or travels through the all-reduced sums, so the ranks hand back together.
         if (mw.status == kCauchyHandBack)
             return cauchy_impl(H, P, x, g, xlow, xupp, delta, s_out, fix_chunks_out, n_breakpoints, n_hmul_out, dev, false);
         H->stats.n_jv += 1;                                          // one read of J

@@ -32,6 +32,11 @@ namespace bh {
 //                                     written exactly as cauchy_sort_scan_kernel writes them
 // Fixed orders everywhere (stated at each kernel), no atomics on doubles: a repeated search is bit-identical.  The bits depend on the
 // grid of kernel 2 (which rows meet in which slab), as the row-stream slabs do.  Hand-back as in form 5.
+//
+// On a row-sharded handle (bh_hess_set_cauchy_rows_ranks) the kernels are the same: kernel 2 runs over this rank's rows (nrows = 0: a
+// grid of 1, no row group, one slab of +0), and between kernels 3 and 4 the host enqueues ONE all-reduce of `red` (2 ld doubles:
+// phi'', then X) — reduce_exchange_kernel with G = 0 or ncclAllReduce (bh_api.hip: cauchy_launch_rows_sorted).  Kernel 4 then runs
+// replicated on identical inputs.
 // ------------------------------------------------------------------------------------------
 constexpr int RS_T = 512;                // threads of cauchy_rowsort_rows_kernel
 constexpr int RS_EPT = 8;                // consecutive ranks a thread owns: a row holds RS_T * RS_EPT = 4096 free entries

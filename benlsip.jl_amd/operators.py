@@ -227,13 +227,19 @@ class AlHessian:
 
     _CAUCHY_ROWS = {"stepwise": _lib.BH_CAUCHY_ROWS_STEPWISE, "sorted": _lib.BH_CAUCHY_ROWS_SORTED}
 
-    def set_cauchy_rows(self, mode):
+    def set_cauchy_rows(self, mode, ranks=None):
         """``bh_hess_set_cauchy_rows``: which box-constrained Cauchy search the implicit form runs — "stepwise" (the default: one
         breakpoint after the other) or "sorted" (the whole search from one sorted sweep over J, ``cauchy_info`` form 6).  Remembered
-        in either form; rebuilds nothing."""
+        in either form; rebuilds nothing.
+
+        ranks (``bh_hess_set_cauchy_rows_ranks``): True lets a row-sharded handle (an active communicator) take the sorted form as
+        well — every rank scans its own rows, ONE all-reduce per search sums phi'' and X; allocates the form's workspace at once.
+        False: a call with a communicator keeps the stepwise path.  None (the default) leaves that switch as it is."""
         if mode not in self._CAUCHY_ROWS:
             raise ValueError("cauchy rows is 'stepwise' or 'sorted', got %r" % (mode,))
         check(_lib.lib().bh_hess_set_cauchy_rows(self._h, self._CAUCHY_ROWS[mode]), "bh_hess_set_cauchy_rows")
+        if ranks is not None:
+            check(_lib.lib().bh_hess_set_cauchy_rows_ranks(self._h, 1 if ranks else 0), "bh_hess_set_cauchy_rows_ranks")
 
     def _get_cauchy_rows(self):
         m, s, c = ct.c_int32(0), ct.c_int32(0), ct.c_int64(0)
@@ -244,6 +250,13 @@ class AlHessian:
     def cauchy_rows(self):
         """"stepwise" or "sorted" (``bh_hess_get_cauchy_rows``)."""
         return {v: k for k, v in self._CAUCHY_ROWS.items()}[self._get_cauchy_rows()[0]]
+
+    @property
+    def cauchy_rows_ranks(self):
+        """Whether the sorted rows search also runs on a row-sharded handle (``bh_hess_get_cauchy_rows_ranks``)."""
+        on = ct.c_int32(0)
+        check(_lib.lib().bh_hess_get_cauchy_rows_ranks(self._h, ct.byref(on)), "bh_hess_get_cauchy_rows_ranks")
+        return bool(on.value)
 
     @property
     def cauchy_rows_served(self):

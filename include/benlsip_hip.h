@@ -265,7 +265,8 @@ int32_t bh_hess_get_cauchy_search(const bh_hess* H, int32_t* mode, int32_t* serv
  *                       (one read of J), stats.n_hmul by nothing.  The step agrees with the other forms to rounding (same active
  *                       set, same counts; bit for bit on exactly representable data); a repeated search is bit-identical; the bits
  *                       may depend on the number of compute units (which rows share a partial sum), as those of H*p do.
- *                       Any other handle or constraint set (Gram form, linear equalities, several ranks, an unserved width) takes
+ *                       Any other handle or constraint set (Gram form, linear equalities, an unserved width; a communicator unless
+ *                       bh_hess_set_cauchy_rows_ranks, below, is on) takes
  *                       the path it takes without the switch, silently and bit for bit; so does a call for whose workspace the
  *                       device has no room.
  *                       Hand-back: as with BH_CAUCHY_SORTED — a non-finite g or a NaN bound on a free variable, or a non-finite
@@ -281,6 +282,31 @@ int32_t bh_hess_get_cauchy_search(const bh_hess* H, int32_t* mode, int32_t* serv
 #define BH_CAUCHY_ROWS_SORTED   1
 int32_t bh_hess_set_cauchy_rows(bh_hess* H, int32_t mode);
 int32_t bh_hess_get_cauchy_rows(const bh_hess* H, int32_t* mode, int32_t* served, int64_t* searches_rows_sorted);
+/* BH_CAUCHY_ROWS_SORTED on a ROW-SHARDED handle.  A switch of its own, 0 (the default) or 1, next to bh_hess_set_cauchy_rows, whose
+ * contract is unchanged: without this switch a call with a communicator keeps the stepwise path (one all-reduce per breakpoint).
+ *   on = 1   a call takes form 6 when ALL of these hold: this switch is 1, bh_hess_set_cauchy_rows is at BH_CAUCHY_ROWS_SORTED, a
+ *            communicator is active, the handle is implicit, there are no linear equalities and the width is served (n <= 4096).
+ *            phi''_k = sum_i w_i S_ik^2 and X_k = sum_i w_i P_ik S_ik are plain sums over the rows of [J; C], and the rows are what the
+ *            ranks hold: every rank scans its own rows (the rows of C on rank 0 only), ONE all-reduce of 2 ld doubles (phi'', then X,
+ *            by segment; 64 KiB at n = 4096) sums them — rank 0's value first, then += rank r, so every rank holds the same bits —
+ *            and the scan runs replicated on identical inputs.  One collective per search instead of one per breakpoint; the launches
+ *            of form 6 plus the exchange (one more launch on the peer-buffer transport, an ncclAllReduce otherwise), the same for
+ *            every search length.  Per completed search on every rank: stats.n_allreduce + 1, stats.n_jv + 1, searches_rows_sorted + 1;
+ *            *n_hmul / n_breakpoints keep form 6's meaning.  A rank without rows takes part with sums of +0.  Replicas are
+ *            bit-identical; against one rank the sums are associated differently (rows meet per rank first), so the step agrees to
+ *            rounding, and bit for bit on exactly representable data.
+ *            Hand-back is collective: its causes (non-finite g, a NaN bound, non-finite phi', phi'' at the stop) are replicated or
+ *            travel through the all-reduced sums, so all ranks re-run the stepwise path together.  An exchange that timed out is
+ *            BH_ERR_RCCL — checked behind every such search, before a counter moves — not a hand-back and not a completed search.
+ *            Setting 1 allocates the workspace of the form at once and returns BH_ERR_HIP when the device has no room (the switch
+ *            stays 0): no rank finds out at search time that it alone must fall back.  For the same reason a search on a
+ *            communicator whose workspace is missing returns BH_ERR_HIP instead of falling back quietly, as one rank does.
+ *   on = 0   every call keeps the path it takes today, bit for bit.  With one process and no communicator the switch changes nothing.
+ * Remembered across bh_hess_set_form.  NULL handle or a value other than 0 / 1: BH_ERR_INVALID_ARG, the state unchanged.  All ranks
+ * must set the same value (like every replicated setting).  Every several-rank figure of this form is a COUNT (launches,
+ * collectives) from several processes on one GPU; no several-rank time has been measured. */
+int32_t bh_hess_set_cauchy_rows_ranks(bh_hess* H, int32_t on);
+int32_t bh_hess_get_cauchy_rows_ranks(const bh_hess* H, int32_t* on);
 int32_t bh_hess_shape(const bh_hess* H, int64_t* d, int64_t* n, int64_t* q);
 /* The compact image of the free columns (option "free_image"): one row per row of the image of J, only the columns of the
  * variables that are free, dense; the box-constrained CG loop of bh_pcg* streams it instead of J.
@@ -389,7 +415,9 @@ int32_t bh_cauchy_step(bh_hess* H, bh_proj* P, const double* x, const double* g,
  *   form 0 = one H*d per breakpoint, 1 = row space of J (box), 2 = row space of J with equalities, 3 = from G in one launch,
  *   form 4 = from G with linear equalities (option "cauchy_gram_eq")
  *   form 5 = from G in one sorted sweep (bh_hess_set_cauchy_search at BH_CAUCHY_SORTED): the same few launches for every search length
- *   form 6 = from J in one sorted sweep (bh_hess_set_cauchy_rows at BH_CAUCHY_ROWS_SORTED): the same few launches for every search length
+ *   form 6 = from J in one sorted sweep (bh_hess_set_cauchy_rows at BH_CAUCHY_ROWS_SORTED): the same few launches for every search length;
+ *            on a row-sharded handle only with bh_hess_set_cauchy_rows_ranks, one all-reduce per search (over the peer buffers the
+ *            exchange is one launch more, counted in n_launches)
  *   n_launches = kernels enqueued by that call (over-launched prologue-only passes included).
  * BH_ERR_PRECONDITION before the first search on the handle. */
 int32_t bh_cauchy_info(const bh_proj* P, int32_t* form, int32_t* n_launches);
