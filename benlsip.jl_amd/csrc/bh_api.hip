@@ -4,6 +4,7 @@
 #include "../../include/benlsip_hip.h"
 #include "bh_cauchy_plan.h"
 #include "bh_cauchy_rows_plan.h"
+#include "bh_cauchy_sort_layout.h"
 #include "bh_free_image_plan.h"
 #include "bh_gram_ingest_plan.h"
 #include "bh_kernels.hip.h"
@@ -3692,14 +3693,11 @@ static CauchyPlan cauchy_make_plan(const bh_hess* H, const bh_proj* P, bool allo
     return p;
 }
 
-// Workspace of the sorted form in doubles: T, b (ld each), the per-panel parts of U and L, the three scan arrays, rank, inv (ints), flag.
-static int64_t cauchy_sort_doubles(int64_t ld) { return (2 + 2 * CS_MAX_PANELS) * ld + 3 * (ld + 16) + ld + 16; }
-static int* cauchy_sort_flag(bh_hess* H) { return reinterpret_cast<int*>(H->csort + (2 + 2 * CS_MAX_PANELS) * H->ld + 3 * (H->ld + 16)) + 2 * H->ld; }
-
-// Workspace of the sorted rows form in doubles: T, b (ld each), phi'' and X (ld each), the scan array, rank, inv (ints), flag; then
-// one slab of 2 ld doubles per workgroup of the row scan.
-static int64_t cauchy_rows_head_doubles(int64_t ld) { return 4 * ld + (ld + 16) + ld + 16; }
-static int* cauchy_rows_flag(bh_hess* H) { return reinterpret_cast<int*>(H->crows + 4 * H->ld + (H->ld + 16)) + 2 * H->ld; }
+// Workspaces of the sorted forms (H->csort: form 5, H->crows: form 6): every offset is bh_cauchy_sort_layout.h's.  The hand-back
+// flag is cleared once behind the allocation; the scan kernel leaves it cleared.
+static hipError_t cauchy_sort_clear_flag(double* base, int64_t ld, CauchyForm form, hipStream_t s) {
+    return hipMemsetAsync(base + cauchy_sort_layout(ld, form, 0).flag, 0, sizeof(int), s);
+}
 static int cauchy_rows_grid(const bh_hess* H, int64_t img_rows) {
     const int64_t groups = (img_rows + RS_R - 1) / RS_R;
     return (int)std::max<int64_t>(1, std::min<int64_t>(groups, (int64_t)RS_GRID_PER_CU * g_ctx.n_cu));
@@ -3710,12 +3708,12 @@ static bool cauchy_rows_workspace(bh_hess* H, hipStream_t s) {
     if (H->crows) return true;
     const int grid = cauchy_rows_grid(H, H->d + H->q);
     void* p = nullptr;
-    if (hipMalloc(&p, (size_t)(cauchy_rows_head_doubles(H->ld) + (int64_t)grid * 2 * H->ld) * sizeof(double)) != hipSuccess) {
+    if (hipMalloc(&p, (size_t)cauchy_sort_layout(H->ld, CAUCHY_ROWS_SORTED, grid).total * sizeof(double)) != hipSuccess) {
         (void)hipGetLastError();
         return false;
     }
     H->crows = static_cast<double*>(p); H->crows_grid = grid;
-    if (hipMemsetAsync(cauchy_rows_flag(H), 0, sizeof(int), s) != hipSuccess) {      // (the scan kernel leaves the flag cleared)
+    if (cauchy_sort_clear_flag(H->crows, H->ld, CAUCHY_ROWS_SORTED, s) != hipSuccess) {
         (void)hipGetLastError();
         dev_free(H->crows);
         H->crows = nullptr; H->crows_grid = 0;
@@ -3752,8 +3750,8 @@ static int32_t cauchy_ensure_buffers(CauchyRun& r) {
     }
     r.sbuf[0] = r.c.w; r.sbuf[1] = r.c.Hp;
     if (r.plan.form == CAUCHY_GRAM_SORTED && !H->csort) {
-        BH_TRY(dev_alloc(&H->csort, cauchy_sort_doubles(H->ld)));
-        BH_HIP(hipMemsetAsync(cauchy_sort_flag(H), 0, sizeof(int), r.s));      // (kernel 3 leaves the flag cleared)
+        BH_TRY(dev_alloc(&H->csort, cauchy_sort_layout(H->ld, CAUCHY_GRAM_SORTED, 0).total));
+        BH_HIP(cauchy_sort_clear_flag(H->csort, H->ld, CAUCHY_GRAM_SORTED, r.s));
     }
     if (r.plan.fused) {
         r.pp = reinterpret_cast<CauchyPass*>(r.img_scal + 8);     // 2 x 32 bytes in the 16-double tail of timg
@@ -4011,59 +4009,50 @@ static int32_t cauchy_launch_pass(CauchyRun& r, int index) {
     }
 }
 
-// The sorted form (bh_cauchysort.hip.h): G made current by the route launch_hmul takes, without a product; then the three launches —
-// the same for every search length.  No host round trip before the final progress word.
-static int32_t cauchy_launch_sorted(CauchyRun& r) {
-    bh_hess* H = r.H;
-    BH_TRY(hess_ready(H));
-    BH_TRY(ensure_gram(H));                                         // G rebuilt first when it is stale, on the same stream
-    const int64_t ld = H->ld;
-    CauchySortArgs sa{};
-    sa.c = r.a; sa.G = H->G; sa.ld = ld;
-    sa.npanels = (int)((ld / 2 + CS_ROW_T * CS_ROW_CPT - 1) / (CS_ROW_T * CS_ROW_CPT));
-    sa.T = H->csort; sa.b = sa.T + ld; sa.UL = sa.b + ld; sa.scan = sa.UL + 2 * CS_MAX_PANELS * ld;
-    sa.rank = reinterpret_cast<int*>(sa.scan + 3 * (ld + 16)); sa.inv = sa.rank + ld; sa.flag = cauchy_sort_flag(H);
-    const int row_groups = (int)((H->n + CS_ROW_R - 1) / CS_ROW_R);
-    const int row_grid = std::max(1, std::min(row_groups, 4 * g_ctx.n_cu / sa.npanels));
-    const int key_tiles = (int)((H->n + CS_RANK_TILE - 1) / CS_RANK_TILE);
-    BH_HIP(hipMemsetAsync(sa.rank, 0, (size_t)ld * sizeof(int), r.s));  // the tiles add their counts into it
-    hipLaunchKernelGGL(cauchy_sort_rank_kernel, dim3((unsigned)((ld + CS_RANK_T - 1) / CS_RANK_T), (unsigned)key_tiles), dim3(CS_RANK_T), 0, r.s, sa);
-    hipLaunchKernelGGL(cauchy_sort_rows_kernel, dim3((unsigned)row_grid, (unsigned)sa.npanels), dim3(CS_ROW_T), 0, r.s, sa);
-    hipLaunchKernelGGL(cauchy_sort_scan_kernel, dim3(1), dim3(CS_SCAN_T), 0, r.s, sa);
-    BH_HIP(hipGetLastError());
-    return BH_OK;
-}
-
-// The sorted rows form (bh_cauchyrowsort.hip.h): ranks, the one read of J, the slab sums, the scan — the same launches for every
-// search length.  No host round trip before the final progress word.
-// With a communicator (bh_hess_set_cauchy_rows_ranks) every rank scans its own img_rows = d + q_eff rows (the rows of C on rank 0
-// only), and phi'', X — plain sums over the rows — are summed over the ranks by ONE all-reduce of 2 ld doubles between the slab sums
-// and the scan: rank 0's value first, then += rank r, the same bits everywhere.  Everything else the scan reads (T, rank, g, the
+// The sorted forms — 5 (bh_cauchysort.hip.h, from G) and 6 (bh_cauchyrowsort.hip.h, from J): keys and ranks, the one read of the
+// matrix, the scan — the same launches for every search length.  No host round trip before the final progress word.
+// Form 5: G is made current by the route launch_hmul takes, without a product.
+// Form 6 with a communicator (bh_hess_set_cauchy_rows_ranks): every rank scans its own img_rows = d + q_eff rows (the rows of C on
+// rank 0 only), and phi'', X — plain sums over the rows — are summed over the ranks by ONE all-reduce of 2 ld doubles between the slab
+// sums and the scan: rank 0's value first, then += rank r, the same bits everywhere.  Everything else the scan reads (T, rank, g, the
 // bounds, the flag of cauchy_init_kernel) is replicated, so the replicas decide alike and a hand-back is collective; a NaN in one
 // rank's rows reaches every rank through the sum.  A rank without rows launches the row scan with a grid of 1 and no row group: one
 // slab of +0.  The exchange is not gated by the loop state: every rank always takes part.
-static int32_t cauchy_launch_rows_sorted(CauchyRun& r) {
+static int32_t cauchy_launch_sorted(CauchyRun& r) {
     bh_hess* H = r.H;
     BH_TRY(hess_ready(H));
+    const bool gram = r.plan.form == CAUCHY_GRAM_SORTED;
+    if (gram) BH_TRY(ensure_gram(H));   // G rebuilt when stale; before the rank kernel, whose hand-back flag only the scan kernel clears
     const int64_t ld = H->ld;
-    CauchyRowSortArgs ra{};
-    CauchySortArgs& sa = ra.s;
-    sa.c = r.a; sa.G = nullptr; sa.ld = ld; sa.UL = nullptr; sa.npanels = 0;
-    sa.T = H->crows; sa.b = sa.T + ld; ra.red = sa.b + ld; sa.scan = ra.red + 2 * ld;
-    sa.rank = reinterpret_cast<int*>(sa.scan + (ld + 16)); sa.inv = sa.rank + ld; sa.flag = cauchy_rows_flag(H);
-    ra.slab = H->crows + cauchy_rows_head_doubles(ld);
-    ra.J = H->Jd; ra.nrows = r.img_rows; ra.d_rows = H->d; ra.mu = H->mu;
-    ra.grid = std::min(cauchy_rows_grid(H, r.img_rows), H->crows_grid);
+    double* w = gram ? H->csort : H->crows;
+    const CauchySortLayout L = cauchy_sort_layout(ld, r.plan.form, 0);
+    CauchySortCore core{};
+    core.c = r.a; core.ld = ld; core.T = w + L.T; core.b = w + L.b;
+    core.rank = reinterpret_cast<int*>(w + L.rank); core.inv = reinterpret_cast<int*>(w + L.inv); core.flag = reinterpret_cast<int*>(w + L.flag);
     const int key_tiles = (int)((H->n + CS_RANK_TILE - 1) / CS_RANK_TILE);
-    BH_HIP(hipMemsetAsync(sa.rank, 0, (size_t)ld * sizeof(int), r.s));  // the tiles add their counts into it
-    hipLaunchKernelGGL(cauchy_sort_rank_kernel, dim3((unsigned)((ld + CS_RANK_T - 1) / CS_RANK_T), (unsigned)key_tiles), dim3(CS_RANK_T), 0, r.s, sa);
-    hipLaunchKernelGGL(cauchy_rowsort_rows_kernel, dim3((unsigned)ra.grid), dim3(RS_T), 0, r.s, ra);
-    hipLaunchKernelGGL(cauchy_rowsort_reduce_kernel, dim3((unsigned)((ld + RS_RED_T - 1) / RS_RED_T), 2u), dim3(RS_RED_T), 0, r.s, ra);
-    if (comm_active()) {
-        BH_HIP(hipGetLastError());
-        BH_TRY(allreduce_inplace(ra.red, 2 * ld, H));                   // phi'', then X, by segment: the one collective of the search
+    BH_HIP(hipMemsetAsync(core.rank, 0, (size_t)ld * sizeof(int), r.s));  // the tiles add their counts into it
+    hipLaunchKernelGGL(cauchy_sort_rank_kernel, dim3((unsigned)((ld + CS_RANK_T - 1) / CS_RANK_T), (unsigned)key_tiles), dim3(CS_RANK_T), 0, r.s, core);
+    if (gram) {
+        CauchySortArgs sa{core};
+        sa.G = H->G; sa.UL = w + L.UL; sa.scan = w + L.scan;
+        sa.npanels = (int)((ld / 2 + CS_ROW_T * CS_ROW_CPT - 1) / (CS_ROW_T * CS_ROW_CPT));
+        const int row_groups = (int)((H->n + CS_ROW_R - 1) / CS_ROW_R);
+        const int row_grid = std::max(1, std::min(row_groups, 4 * g_ctx.n_cu / sa.npanels));
+        hipLaunchKernelGGL(cauchy_sort_rows_kernel, dim3((unsigned)row_grid, (unsigned)sa.npanels), dim3(CS_ROW_T), 0, r.s, sa);
+        hipLaunchKernelGGL(cauchy_sort_scan_kernel, dim3(1), dim3(CS_SCAN_T), 0, r.s, sa);
+    } else {
+        CauchyRowSortArgs ra{core};
+        ra.scan = w + L.scan; ra.red = w + L.red; ra.slab = w + L.slab;
+        ra.J = H->Jd; ra.nrows = r.img_rows; ra.d_rows = H->d; ra.mu = H->mu;
+        ra.grid = std::min(cauchy_rows_grid(H, r.img_rows), H->crows_grid);
+        hipLaunchKernelGGL(cauchy_rowsort_rows_kernel, dim3((unsigned)ra.grid), dim3(RS_T), 0, r.s, ra);
+        hipLaunchKernelGGL(cauchy_rowsort_reduce_kernel, dim3((unsigned)((ld + RS_RED_T - 1) / RS_RED_T), 2u), dim3(RS_RED_T), 0, r.s, ra);
+        if (comm_active()) {
+            BH_HIP(hipGetLastError());
+            BH_TRY(allreduce_inplace(ra.red, 2 * ld, H));                   // phi'', then X, by segment: the one collective of the search
+        }
+        hipLaunchKernelGGL(cauchy_rowsort_scan_kernel, dim3(1), dim3(CS_SCAN_T), 0, r.s, ra);
     }
-    hipLaunchKernelGGL(cauchy_rowsort_scan_kernel, dim3(1), dim3(CS_SCAN_T), 0, r.s, ra);
     BH_HIP(hipGetLastError());
     return BH_OK;
 }
@@ -4140,28 +4129,21 @@ static int32_t cauchy_impl(bh_hess* H, bh_proj* P, const double* x, const double
     hipLaunchKernelGGL(cauchy_init_kernel, dim3(1), dim3(CG_T), 0, s, a);
     if (mA > 0) BH_TRY(launch_reduced_factor(P, true, nullptr));
     MirrorWord mw{};
-    if (plan.form == CAUCHY_GRAM_SORTED) {
+    if (plan.form == CAUCHY_GRAM_SORTED || plan.form == CAUCHY_ROWS_SORTED) {
+        const bool rows = plan.form == CAUCHY_ROWS_SORTED;
         BH_TRY(cauchy_launch_sorted(run));
         BH_TRY(wait_mirror(c, a.tag, plan.max_pass, &mw));           // published once, by the scan kernel
-        // a non-finite g, a NaN bound or a non-finite phi', phi'' at the stop: this call runs on the path the handle takes with
-        // BH_CAUCHY_STEPWISE — codes and bits are that path's; it is not counted as a sorted search
+        // Form 6: an exchange that timed out delivers NaN in the segments of the workgroups that gave up: behind the stop they go
+        // unseen, at or before it they look like a hand-back.  Either way the call is BH_ERR_RCCL before a counter moves — not a
+        // completed search, and not a stepwise re-run on a dead transport.  (The scan kernel runs behind the exchange: the word is final.)
+        if (rows && comm_active()) BH_TRY(check_peer_error());
+        // a non-finite g, a NaN bound of a free variable or a non-finite phi', phi'' at the stop: this call runs on the stepwise path
+        // with both sorted forms off — codes and bits are that path's; it is not counted as a sorted search.  With a communicator
+        // every cause is replicated or travels through the all-reduced sums, so the ranks hand back together.
         if (mw.status == kCauchyHandBack)
             return cauchy_impl(H, P, x, g, xlow, xupp, delta, s_out, fix_chunks_out, n_breakpoints, n_hmul_out, dev, false);
-        H->stats.n_hmul += 1;                                        // one read of G
-        H->searches_sorted += 1;
-    } else if (plan.form == CAUCHY_ROWS_SORTED) {
-        BH_TRY(cauchy_launch_rows_sorted(run));
-        BH_TRY(wait_mirror(c, a.tag, plan.max_pass, &mw));           // published once, by the scan kernel
-        // An exchange that timed out delivers NaN in the segments of the workgroups that gave up: behind the stop they go unseen, at
-        // or before it they look like a hand-back.  Either way the call is BH_ERR_RCCL before a counter moves — not a completed
-        // search, and not a stepwise re-run on a dead transport.  (The scan kernel runs behind the exchange: the word is final.)
-        if (comm_active()) BH_TRY(check_peer_error());
-        // hand-back as in form 5: this call runs on the stepwise path with both sorted forms off — codes and bits are that path's.
-        // With a communicator every cause is replicated or travels through the all-reduced sums, so the ranks hand back together.
-        if (mw.status == kCauchyHandBack)
-            return cauchy_impl(H, P, x, g, xlow, xupp, delta, s_out, fix_chunks_out, n_breakpoints, n_hmul_out, dev, false);
-        H->stats.n_jv += 1;                                          // one read of J
-        H->searches_rows_sorted += 1;
+        (rows ? H->stats.n_jv : H->stats.n_hmul) += 1;               // one read of J, or of G
+        (rows ? H->searches_rows_sorted : H->searches_sorted) += 1;
     } else if (plan.form == CAUCHY_GRAM) {
         const int launched = plan.max_pass, off = plan.sched.off;   // one launch stands for every pass; off = 0 (not the one-kernel row-space form)
         BH_TRY(launch_hmul(H, c.p, c.Hp, c.d_state, -1));           // Hd = H*d    :609  (rebuilds G first when it is stale)

@@ -29,13 +29,13 @@ namespace bh {
 //                                     per-workgroup accumulators; one slab of 2 ld doubles per workgroup
 //   3. cauchy_rowsort_reduce_kernel   the slabs summed over the workgroups in ascending order: phi''_k, X_k
 //   4. cauchy_rowsort_scan_kernel     one workgroup: the suffix sums of g d, every decision, s_c, d, the active set, the loop state —
-//                                     written exactly as cauchy_sort_scan_kernel writes them
+//                                     by the functions cauchy_sort_scan_kernel calls (cauchy_sort_stop, cauchy_sort_finish)
 // Fixed orders everywhere (stated at each kernel), no atomics on doubles: a repeated search is bit-identical.  The bits depend on the
-// grid of kernel 2 (which rows meet in which slab), as the row-stream slabs do.  Hand-back as in form 5.
+// grid of kernel 2 (which rows meet in which slab), as the row-stream slabs do.  Hand-back as in form 5: one code path.
 //
 // On a row-sharded handle (bh_hess_set_cauchy_rows_ranks) the kernels are the same: kernel 2 runs over this rank's rows (nrows = 0: a
 // grid of 1, no row group, one slab of +0), and between kernels 3 and 4 the host enqueues ONE all-reduce of `red` (2 ld doubles:
-// phi'', then X) — reduce_exchange_kernel with G = 0 or ncclAllReduce (bh_api.hip: cauchy_launch_rows_sorted).  Kernel 4 then runs
+// phi'', then X) — reduce_exchange_kernel with G = 0 or ncclAllReduce (bh_api.hip: cauchy_launch_sorted).  Kernel 4 then runs
 // replicated on identical inputs.
 // ------------------------------------------------------------------------------------------
 constexpr int RS_T = 512;                // threads of cauchy_rowsort_rows_kernel
@@ -46,8 +46,8 @@ constexpr int RS_GRID_PER_CU = 1;        // persistent grid: min(row groups, RS_
 constexpr int RS_RED_T = 256;            // threads of cauchy_rowsort_reduce_kernel: one segment each
 static_assert(RS_MAXN == 4096, "bh_cauchy_rows_plan.h: kCauchyRowsMaxN");
 
-struct CauchyRowSortArgs {
-    CauchySortArgs s;            // c, T, b, rank, inv, flag, ld as in form 5; G, UL unused; scan: [ld + 16] suffix of g d inside a thread's block
+struct CauchyRowSortArgs : CauchySortCore {
+    double* scan;                // [ld + 16] by rank: suffix of g d inside a thread's block
     const double* J; int64_t nrows, d_rows; double mu;      // the image: nrows x ld row-major, the rows >= d_rows are those of C
     double* slab;                // [grid][2][ld] by segment: w S^2, then w P S, of the rows of one workgroup
     double* red;                 // [2][ld] by segment: phi''_k, X_k
@@ -70,11 +70,11 @@ __global__ __launch_bounds__(RS_T) void cauchy_rowsort_rows_kernel(CauchyRowSort
     __shared__ __attribute__((aligned(16))) double rowbuf[R][RS_MAXN];
     __shared__ unsigned short sinv[RS_MAXN];                          // rank -> column (0xffff: none); columns are below 4096
     __shared__ double wt[2][R][NW];
-    const CauchyArgs& a = ra.s.c;
+    const CauchyArgs& a = ra.c;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = a.n;
     const int nfree = n - a.st->iter;                                  // (cauchy_init_kernel: the variables fixed at the start)
-    const int64_t ld = ra.s.ld, ld2 = ld >> 1;
+    const int64_t ld = ra.ld, ld2 = ld >> 1;
     const double2* __restrict__ J2 = reinterpret_cast<const double2*>(ra.J);
     const int ngroups = (int)((ra.nrows + R - 1) / R);
     const int NG = (int)gridDim.x;
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(RS_T) void cauchy_rowsort_rows_kernel(CauchyRowSort
 #pragma unroll
     for (int c = 0; c < CPT; ++c) {
         rk[c] = make_int2(-1, -1);
-        if (act[c]) rk[c] = reinterpret_cast<const int2*>(ra.s.rank)[tid + c * T];
+        if (act[c]) rk[c] = reinterpret_cast<const int2*>(ra.rank)[tid + c * T];
         if (rk[c].x >= RS_MAXN) rk[c].x = -1;                          // (never: ranks are below nfree <= n <= RS_MAXN)
         if (rk[c].y >= RS_MAXN) rk[c].y = -1;
     }
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(RS_T) void cauchy_rowsort_rows_kernel(CauchyRowSort
         const int r = tid * E + e;
         const int i = r < nfree && sinv[r] != 0xffffu ? (int)sinv[r] : -1;
         dr[e] = i >= 0 ? a.d[i] : 0.0;                                 // d_r = -g_r (cauchy_init_kernel)
-        br[e] = i >= 0 ? ra.s.b[i] : 0.0;                              // b_r: 0 unless T_r is finite
+        br[e] = i >= 0 ? ra.b[i] : 0.0;                              // b_r: 0 unless T_r is finite
     }
     double accS[E], accX[E];
 #pragma unroll
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(RS_T) void cauchy_rowsort_rows_kernel(CauchyRowSort
 
 // 3. The slabs over the workgroups of kernel 2 in ascending order from +0; workgroup (x, y): segment 256 x + tid of sum y.
 __global__ __launch_bounds__(RS_RED_T) void cauchy_rowsort_reduce_kernel(CauchyRowSortArgs ra) {
-    const int64_t ld = ra.s.ld;
+    const int64_t ld = ra.ld;
     const int64_t k = (int64_t)blockIdx.x * RS_RED_T + threadIdx.x;
     if (k >= ld) return;
     const double* p = ra.slab + (int64_t)blockIdx.y * ld + k;
@@ -219,113 +219,53 @@ __global__ __launch_bounds__(RS_RED_T) void cauchy_rowsort_reduce_kernel(CauchyR
     ra.red[(int64_t)blockIdx.y * ld + k] = acc;
 }
 
-// phi', phi'', theta and the decision of segment k: the arithmetic and rounding order of cauchy_sort_segment, with phi''_k and X_k
-// as kernel 3 left them (segment nfree: both +0).
-__device__ __forceinline__ CauchySortSeg cauchy_rowsort_segment(const CauchyRowSortArgs& ra, int k, int nfree, int nfix0, double offG) {
-    const CauchySortArgs& sa = ra.s;
-    const double INF = __longlong_as_double(0x7ff0000000000000ll);
-    CauchySortSeg o;
-    o.phi_pp = k < nfree ? ra.red[k] : 0.0;
-    const double X = k < nfree ? ra.red[sa.ld + k] : 0.0;
-    const double gd = __dadd_rn(sa.scan[k], offG);
-    o.t_prev = k > 0 ? sa.T[sa.inv[k - 1]] : 0.0;
-    const int ik = k < nfree ? sa.inv[k] : -1;
-    const double tk = ik >= 0 ? sa.T[ik] : INF;
-    const bool fin = fabs(tk) < INF;
-    o.theta = fin ? __dsub_rn(tk, o.t_prev) : INF;
-    o.ind = fin ? ik : -1;
-    o.phi_p = __dadd_rn(__dadd_rn(gd, X), __dmul_rn(o.t_prev, o.phi_pp));
-    o.bad = !(fabs(o.phi_p) < INF) || !(fabs(o.phi_pp) < INF);
-    o.q = cauchy_decide(o.phi_p, o.phi_pp, o.theta, o.ind, nfix0 + k, sa.c.nmm);       // :615-636
-    return o;
-}
-
-// 4. Scan, decision, write-back: one workgroup of 1024 threads, the shape of cauchy_sort_scan_kernel.  Thread t owns the block of
-// E = ceil((n + 1) / 1024) consecutive segments.  sum_{r >= k} g_r d_r in that kernel's order: inside a block descending from +0
-// (W_k = g_k d_k + W_{k+1}); the block totals behind lane l from lane 63 downwards; the wave totals behind wave w from wave 15
-// downwards; the sum is W_k + (A + B).  s, d, the active set, CgState and the progress word as that kernel writes them.
+// 4. Scan, decision, write-back: one workgroup of 1024 threads, the tail of cauchy_sort_scan_kernel (bh_cauchysort.hip.h) called,
+// not restated.  Thread t owns the block of E = ceil((n + 1) / 1024) consecutive segments.  sum_{r >= k} g_r d_r in that kernel's
+// order: inside a block descending from +0 (W_k = g_k d_k + W_{k+1}); the block totals behind lane l from lane 63 downwards; the
+// wave totals behind wave w from wave 15 downwards; the sum is W_k + (A + B).  phi''_k and X_k as kernel 3 left them (segment
+// nfree: both +0).
 __global__ __launch_bounds__(CS_SCAN_T) void cauchy_rowsort_scan_kernel(CauchyRowSortArgs ra) {
     constexpr int T = CS_SCAN_T, NW = T / 64;
     __shared__ double totG[T];
     __shared__ double wtG[NW];
     __shared__ int kmin, nan_bound;
-    const CauchySortArgs& sa = ra.s;
-    const CauchyArgs& a = sa.c;
-    CgState* st = a.st;
+    const CauchyArgs& a = ra.c;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = a.n;
-    const int nfix0 = st->iter, nfree = n - nfix0;
-    const int flag_in = *sa.flag;
+    const int nfix0 = a.st->iter, nfree = n - nfix0;
+    const int flag_in = *ra.flag;
     const int E = (n + 1 + T - 1) / T;
     const int lo = min(tid * E, nfree + 1), hi = min(lo + E, nfree + 1);
     if (tid == 0) { kmin = 0x7fffffff; nan_bound = 0; }
-    bool nb = false;
-    for (int i = tid; i < n; i += T) {                                // the inverse permutation (read below behind the barrier)
-        const int r = sa.rank[i];
-        if (r >= 0) {
-            sa.inv[r] = i;
-            // a NaN bound of a free variable: d_l, d_u hide it (fmax, fmin of cauchy_init_kernel drop a NaN operand) — hand back
-            nb = nb || a.xlow[i] != a.xlow[i] || a.xupp[i] != a.xupp[i];
-        }
-    }
+    const bool nb = cauchy_sort_invert(ra);
     __syncthreads();
     if (nb) nan_bound = 1;                                             // (every writer stores the same value; read behind two more barriers)
     double wg = 0.0;
     for (int k = hi - 1; k >= lo; --k) {
         double t = 0.0;
-        if (k < nfree) { const double gi = a.g[sa.inv[k]]; t = __dmul_rn(gi, -gi); }
+        if (k < nfree) { const double gi = a.g[ra.inv[k]]; t = __dmul_rn(gi, -gi); }
         wg = __dadd_rn(t, wg);
-        sa.scan[k] = wg;
+        ra.scan[k] = wg;
     }
     totG[tid] = wg;
     __syncthreads();
-    double aG = 0.0;
-    for (int u = 63; u > lane; --u) aG = __dadd_rn(totG[64 * wave + u], aG);
-    if (lane == 0) wtG[wave] = __dadd_rn(wg, aG);
+    double aG[1], bG[1];
+    cauchy_carry_behind(totG + 64 * wave, T, 63, lane, aG);
+    if (lane == 0) wtG[wave] = __dadd_rn(wg, aG[0]);
     __syncthreads();
-    double bG = 0.0;
-    for (int v = NW - 1; v > wave; --v) bG = __dadd_rn(wtG[v], bG);
-    const double offG = __dadd_rn(aG, bG);
+    cauchy_carry_behind(wtG, NW, NW - 1, wave, bG);
+    const double offG = __dadd_rn(aG[0], bG[0]);
     totG[tid] = offG;                                                  // (every read of the block totals lies before the barrier above)
-    int first = 0x7fffffff;
+    auto segment = [&](int k, double oG) {
+        return cauchy_sort_stop(ra, k, nfree, nfix0, k < nfree ? ra.red[k] : 0.0, k < nfree ? ra.red[ra.ld + k] : 0.0, __dadd_rn(ra.scan[k], oG));
+    };
     for (int k = lo; k < hi; ++k) {
-        const CauchySortSeg sg = cauchy_rowsort_segment(ra, k, nfree, nfix0, offG);
-        if (sg.q.done || sg.bad) { first = k; break; }
+        const CauchySortSeg sg = segment(k, offG);
+        if (sg.q.done || sg.bad) { atomicMin(&kmin, k); break; }
     }
-    if (first != 0x7fffffff) atomicMin(&kmin, first);
     __syncthreads();
     const int ks = kmin;                                               // (segment nfree always ends the search: nfix0 + nfree = n)
-    const int owner = ks / E;
-    const CauchySortSeg sg = cauchy_rowsort_segment(ra, ks, nfree, nfix0, totG[owner]);
-    if (flag_in != 0 || sg.bad || nan_bound != 0) {                    // hand-back: nothing of the search is written
-        if (tid == 0) {
-            *sa.flag = 0;
-            st->done = 1; st->need_proj = 0;
-            publish_cauchy_word(a, kCauchyHandBack, 1, 0, 1);
-        }
-        return;
-    }
-    const double step = sg.q.step, tstar = sg.t_prev;
-    for (int i = tid; i < n; i += T) {
-        const int r = sa.rank[i];
-        if (r < 0) continue;                                           // fixed at the start: s_c = +0, d = 0 (cauchy_init_kernel)
-        if (r < ks) {
-            a.s[i] = sa.b[i];
-            a.d[i] = 0.0; a.fixrank[i] = 0;                            // add_active!: fixvars[i] = true (poly:246); d_i = 0 (:632)
-        } else {
-            const double di = -a.g[i];
-            a.s[i] = __dadd_rn(__dadd_rn(0.0, __dmul_rn(tstar, di)), __dmul_rn(step, di));     // :628 per segment, then :625
-        }
-    }
-    if (tid == 0) {
-        st->rtv = sg.phi_p; st->pHp = sg.phi_pp; st->gamma = sg.theta; st->alpha = sg.q.delta_t;
-        st->n_hmul = ks + 1;
-        st->approx_solved = sg.q.min_found; st->neg_curvature = sg.q.err;
-        st->iter = nfix0 + ks; st->pad = ks;
-        if (ks > 0) { const int il = sa.inv[ks - 1]; st->status = il; st->beta = -a.g[il]; }
-        st->done = 1; st->need_proj = 0;
-        publish_cauchy_word(a, sg.q.err, 1, ks, ks + 1);
-    }
+    cauchy_sort_finish(ra, segment(ks, totG[ks / E]), ks, nfix0, flag_in != 0 || nan_bound != 0);
 }
 
 }  // namespace bh

@@ -6,6 +6,7 @@
 #include "bh_reduce.hip.h"
 #include "bh_cg.hip.h"
 #include "bh_cauchy.hip.h"
+#include "bh_cauchy_sort_layout.h"
 
 namespace bh {
 
@@ -29,8 +30,8 @@ namespace bh {
 //   3. cauchy_sort_scan_kernel   one workgroup: the suffix / prefix sums, every decision, s_c, d, the active set, the loop state
 // Fixed orders everywhere (stated at each kernel), no atomics on doubles (the counts of kernel 1 are integers: their sum does not
 // depend on the order): the bits do not depend on the grid, and a repeated search is bit-identical.  A non-finite g, a NaN bound
-// or a non-finite phi', phi'' at the stop raises the hand-back code in the progress word: the host runs that call again on the
-// stepwise path.
+// of a free variable or a non-finite phi', phi'' at the stop raises the hand-back code in the progress word: the host runs that
+// call again on the stepwise path.  The sorted rows form (bh_cauchyrowsort.hip.h) calls kernel 1 and the tail of kernel 3.
 // ------------------------------------------------------------------------------------------
 constexpr int CS_RANK_T = 256;           // threads of cauchy_sort_rank_kernel: one key each
 constexpr int CS_RANK_TILE = 512;        // keys per LDS tile: workgroup (x, y) counts the keys of tile y
@@ -41,14 +42,21 @@ constexpr int CS_MAX_PANELS = 4;         // n <= 16384
 constexpr int CS_SCAN_T = 1024;          // threads of cauchy_sort_scan_kernel
 constexpr int kCauchyHandBack = 8;       // error field of the progress word: run this call on the stepwise path
 
-struct CauchySortArgs {
-    CauchyArgs c;                // st, g, d, s, dl, du, fixrank, n, nmm, mirror, tag (as left by cauchy_init_kernel)
-    const double* G; int64_t ld; // ld x ld row-major, padding rows and columns zero
+static_assert(CS_MAX_PANELS == kCauchySortMaxPanels, "bh_cauchy_sort_layout.h: kCauchySortMaxPanels");
+
+// What the keys, the stop and the write-back need: shared with the sorted rows form (bh_cauchyrowsort.hip.h).
+struct CauchySortCore {
+    CauchyArgs c;                // st, g, d, s, dl, du, xlow, xupp, fixrank, n, nmm, mirror, tag (as left by cauchy_init_kernel)
+    int64_t ld;                  // padded width
     double* T; double* b;        // by index (ld each): T_i (NaN: fixed at the start), b_i (0 unless T_i is finite)
-    int* rank; int* inv;         // rank[i] (-1: fixed at the start or padding; zeroed before kernel 1), inv[rank] = i (kernel 3)
+    int* rank; int* inv;         // rank[i] (-1: fixed at the start or padding; zeroed before kernel 1), inv[rank] = i (the scan kernel)
+    int* flag;                   // hand-back flag of kernel 1 (cleared again by the scan kernel)
+};
+
+struct CauchySortArgs : CauchySortCore {
+    const double* G;             // ld x ld row-major, padding rows and columns zero
     double* UL;                  // [2][npanels][ld] by rank: the per-panel parts of U, then of L
     double* scan;                // [3][ld + 16] by rank: prefix of c, suffix of shell, suffix of g d inside a thread's block
-    int* flag;                   // hand-back flag of kernel 1 (cleared again by kernel 3)
     int npanels;
 };
 
@@ -73,7 +81,7 @@ __device__ __forceinline__ double cauchy_sort_key(const CauchyArgs& a, int i, do
 // 1. Keys and ranks.  Workgroup (x, y): thread tid owns index i = 256 x + tid < ld and counts the keys of tile y (512 keys, formed by
 // the workgroup, 2 per thread) that come before its own: broadcast LDS reads, integer counts added into rank[i] (zero before the
 // launch) — deterministic, no sort network; 1 + (n - 1) / 512 tiles spread the n^2 comparisons over the chip.
-__global__ __launch_bounds__(CS_RANK_T) void cauchy_sort_rank_kernel(CauchySortArgs sa) {
+__global__ __launch_bounds__(CS_RANK_T) void cauchy_sort_rank_kernel(CauchySortCore sa) {
     __shared__ __attribute__((aligned(16))) double tile[CS_RANK_TILE];
     const CauchyArgs& a = sa.c;
     const int n = a.n, tid = threadIdx.x;
@@ -238,94 +246,66 @@ __device__ __forceinline__ CauchySortTerm cauchy_sort_term(const CauchySortArgs&
     return t;
 }
 
-// phi', phi'', theta and the decision of segment k from the scanned sums.
+// ---- the tail both sorted forms share (one workgroup of CS_SCAN_T threads; the kernels own the barriers) -------------------------
+// The inverse permutation, this thread's indices (read behind the caller's barrier).  True: a free variable of this thread has a
+// NaN bound.  d_l, d_u hide it (fmax, fmin of cauchy_init_kernel drop a NaN operand), so the keys cannot see it: hand back.
+__device__ __forceinline__ bool cauchy_sort_invert(const CauchySortCore& sa) {
+    const CauchyArgs& a = sa.c;
+    bool nan_bound = false;
+    for (int i = threadIdx.x; i < a.n; i += CS_SCAN_T) {
+        const int r = sa.rank[i];
+        const double lo = a.xlow[i], up = a.xupp[i];                    // (beside the rank load, not behind it)
+        if (r >= 0) {
+            sa.inv[r] = i;
+            nan_bound = nan_bound || lo != lo || up != up;
+        }
+    }
+    return nan_bound;
+}
+
+// Carries of N arrays of totals (array j at tot + j * stride), each a chain of its own, from +0: the totals behind position pos
+// from position `last` downwards (acc = tot + acc), and the totals before pos from position 0 upwards (acc = acc + tot).  The lanes
+// of a wave carry the block totals (last = 63), the waves carry the wave totals (last = 15).
+template <int N>
+__device__ __forceinline__ void cauchy_carry_behind(const double* tot, int stride, int last, int pos, double (&acc)[N]) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) acc[j] = 0.0;
+    for (int u = last; u > pos; --u)
+#pragma unroll
+        for (int j = 0; j < N; ++j) acc[j] = __dadd_rn(tot[j * stride + u], acc[j]);
+}
+__device__ __forceinline__ double cauchy_carry_before(const double* tot, int pos) {
+    double acc = 0.0;
+    for (int u = 0; u < pos; ++u) acc = __dadd_rn(acc, tot[u]);
+    return acc;
+}
+
+// phi', theta and the decision of segment k from phi''_k, the cross term (sum_{r < k} c_r, or X_k) and sum_{r >= k} g_r d_r.
 struct CauchySortSeg { double phi_p, phi_pp, theta, t_prev; int ind; bool bad; CauchyDecision q; };
-__device__ __forceinline__ CauchySortSeg cauchy_sort_segment(const CauchySortArgs& sa, int k, int nfree, int nfix0, double offC, double offS,
-                                                             double offG) {
+__device__ __forceinline__ CauchySortSeg cauchy_sort_stop(const CauchySortCore& sa, int k, int nfree, int nfix0, double phi_pp, double cross,
+                                                          double gd) {
     const double INF = __longlong_as_double(0x7ff0000000000000ll);
-    const int64_t sl = sa.ld + 16;
     CauchySortSeg o;
-    o.phi_pp = __dadd_rn(sa.scan[sl + k], offS);
-    const double gd = __dadd_rn(sa.scan[2 * sl + k], offG);
-    const double cc = __dadd_rn(offC, sa.scan[k]);
+    o.phi_pp = phi_pp;
     o.t_prev = k > 0 ? sa.T[sa.inv[k - 1]] : 0.0;
     const int ik = k < nfree ? sa.inv[k] : -1;
     const double tk = ik >= 0 ? sa.T[ik] : INF;
     const bool fin = fabs(tk) < INF;
     o.theta = fin ? __dsub_rn(tk, o.t_prev) : INF;
     o.ind = fin ? ik : -1;
-    o.phi_p = __dadd_rn(__dadd_rn(gd, cc), __dmul_rn(o.t_prev, o.phi_pp));
+    o.phi_p = __dadd_rn(__dadd_rn(gd, cross), __dmul_rn(o.t_prev, o.phi_pp));
     o.bad = !(fabs(o.phi_p) < INF) || !(fabs(o.phi_pp) < INF);
     o.q = cauchy_decide(o.phi_p, o.phi_pp, o.theta, o.ind, nfix0 + k, sa.c.nmm);       // :615-636
     return o;
 }
 
-// 3. Scan, decision, write-back: one workgroup of 1024 threads.  Thread t owns the block of E = ceil((n + 1) / 1024) consecutive
-// segments k = t E .. t E + E - 1 (k <= nfree).  The fixed order of the sums:
-//   inside a block   prefix of c ascending from +0 (P_k = sum of c_r, lo <= r < k); suffix of shell and of g d descending from +0
-//                    (W_k = term_k + W_{k+1});
-//   inside a wave    the block totals behind lane l from lane 63 downwards (A = tot + A), before lane l from lane 0 upwards;
-//   across waves     the wave totals behind wave w from wave 15 downwards, before wave w from wave 0 upwards;
-//   phi''_k = W_k + (A + B),  sum_{r >= k} g_r d_r likewise,  sum_{r < k} c_r = (B + A) + P_k.
-__global__ __launch_bounds__(CS_SCAN_T) void cauchy_sort_scan_kernel(CauchySortArgs sa) {
-    constexpr int T = CS_SCAN_T, NW = T / 64;
-    __shared__ double totC[T], totS[T], totG[T];
-    __shared__ double wtC[NW], wtS[NW], wtG[NW];
-    __shared__ int kmin;
+// The end of the search at segment ks (sg: its stop).  Hand-back: nothing of the search is written.  Else s_c, d, the active set,
+// the loop state and the progress word.
+__device__ __forceinline__ void cauchy_sort_finish(const CauchySortCore& sa, const CauchySortSeg& sg, int ks, int nfix0, bool hand_back) {
     const CauchyArgs& a = sa.c;
     CgState* st = a.st;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = a.n;
-    const int nfix0 = st->iter, nfree = n - nfix0;
-    const int flag_in = *sa.flag;
-    const int64_t sl = sa.ld + 16;
-    const int E = (n + 1 + T - 1) / T;
-    const int lo = min(tid * E, nfree + 1), hi = min(lo + E, nfree + 1);
-    if (tid == 0) kmin = 0x7fffffff;
-    for (int i = tid; i < n; i += T) {                                // the inverse permutation (read below behind the barrier)
-        const int r = sa.rank[i];
-        if (r >= 0) sa.inv[r] = i;
-    }
-    __syncthreads();
-    // ---- the terms of this block: prefix of c ascending; shell and g d parked, then their suffixes descending --------------------
-    double p = 0.0;
-    for (int k = lo; k < hi; ++k) {
-        sa.scan[k] = p;
-        CauchySortTerm t{0.0, 0.0, 0.0};
-        if (k < nfree) t = cauchy_sort_term(sa, k);
-        p = __dadd_rn(p, t.c);
-        sa.scan[sl + k] = t.shell; sa.scan[2 * sl + k] = t.gd;
-    }
-    double ws = 0.0, wg = 0.0;
-    for (int k = hi - 1; k >= lo; --k) {
-        ws = __dadd_rn(sa.scan[sl + k], ws); wg = __dadd_rn(sa.scan[2 * sl + k], wg);
-        sa.scan[sl + k] = ws; sa.scan[2 * sl + k] = wg;
-    }
-    totC[tid] = p; totS[tid] = ws; totG[tid] = wg;
-    __syncthreads();
-    double aC = 0.0, aS = 0.0, aG = 0.0;
-    for (int u = 0; u < lane; ++u) aC = __dadd_rn(aC, totC[64 * wave + u]);
-    for (int u = 63; u > lane; --u) { aS = __dadd_rn(totS[64 * wave + u], aS); aG = __dadd_rn(totG[64 * wave + u], aG); }
-    if (lane == 63) wtC[wave] = __dadd_rn(aC, p);
-    if (lane == 0) { wtS[wave] = __dadd_rn(ws, aS); wtG[wave] = __dadd_rn(wg, aG); }
-    __syncthreads();
-    double bC = 0.0, bS = 0.0, bG = 0.0;
-    for (int v = 0; v < wave; ++v) bC = __dadd_rn(bC, wtC[v]);
-    for (int v = NW - 1; v > wave; --v) { bS = __dadd_rn(wtS[v], bS); bG = __dadd_rn(wtG[v], bG); }
-    const double offC = __dadd_rn(bC, aC), offS = __dadd_rn(aS, bS), offG = __dadd_rn(aG, bG);
-    totC[tid] = offC; totS[tid] = offS; totG[tid] = offG;             // (every read of the block totals lies before the barrier above)
-    // ---- the first segment of this block at which the search ends ----------------------------------------------------------------
-    int first = 0x7fffffff;
-    for (int k = lo; k < hi; ++k) {
-        const CauchySortSeg sg = cauchy_sort_segment(sa, k, nfree, nfix0, offC, offS, offG);
-        if (sg.q.done || sg.bad) { first = k; break; }
-    }
-    if (first != 0x7fffffff) atomicMin(&kmin, first);
-    __syncthreads();
-    const int ks = kmin;                                               // (segment nfree always ends the search: nfix0 + nfree = n)
-    const int owner = ks / E;
-    const CauchySortSeg sg = cauchy_sort_segment(sa, ks, nfree, nfix0, totC[owner], totS[owner], totG[owner]);
-    if (flag_in != 0 || sg.bad) {                                      // hand-back: nothing of the search is written
+    const int tid = threadIdx.x;
+    if (hand_back || sg.bad) {
         if (tid == 0) {
             *sa.flag = 0;
             st->done = 1; st->need_proj = 0;
@@ -333,9 +313,8 @@ __global__ __launch_bounds__(CS_SCAN_T) void cauchy_sort_scan_kernel(CauchySortA
         }
         return;
     }
-    // ---- s_c, d and the active set ---------------------------------------------------------------------------------------------
     const double step = sg.q.step, tstar = sg.t_prev;
-    for (int i = tid; i < n; i += T) {
+    for (int i = tid; i < a.n; i += CS_SCAN_T) {
         const int r = sa.rank[i];
         if (r < 0) continue;                                           // fixed at the start: s_c = +0, d = 0 (cauchy_init_kernel)
         if (r < ks) {
@@ -355,6 +334,70 @@ __global__ __launch_bounds__(CS_SCAN_T) void cauchy_sort_scan_kernel(CauchySortA
         st->done = 1; st->need_proj = 0;
         publish_cauchy_word(a, sg.q.err, 1, ks, ks + 1);
     }
+}
+
+// 3. Scan, decision, write-back: one workgroup of 1024 threads.  Thread t owns the block of E = ceil((n + 1) / 1024) consecutive
+// segments k = t E .. t E + E - 1 (k <= nfree).  The fixed order of the sums:
+//   inside a block   prefix of c ascending from +0 (P_k = sum of c_r, lo <= r < k); suffix of shell and of g d descending from +0
+//                    (W_k = term_k + W_{k+1});
+//   inside a wave    the block totals behind lane l from lane 63 downwards (A = tot + A), before lane l from lane 0 upwards;
+//   across waves     the wave totals behind wave w from wave 15 downwards, before wave w from wave 0 upwards;
+//   phi''_k = W_k + (A + B),  sum_{r >= k} g_r d_r likewise,  sum_{r < k} c_r = (B + A) + P_k.
+__global__ __launch_bounds__(CS_SCAN_T) void cauchy_sort_scan_kernel(CauchySortArgs sa) {
+    constexpr int T = CS_SCAN_T, NW = T / 64;
+    __shared__ double totC[T], totD[2][T];                            // block totals: c; shell and g d (the descending pair)
+    __shared__ double wtC[NW], wtD[2][NW];
+    __shared__ int kmin, nan_bound;
+    const CauchyArgs& a = sa.c;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = a.n;
+    const int nfix0 = a.st->iter, nfree = n - nfix0;
+    const int flag_in = *sa.flag;
+    const int64_t sl = sa.ld + 16;
+    const int E = (n + 1 + T - 1) / T;
+    const int lo = min(tid * E, nfree + 1), hi = min(lo + E, nfree + 1);
+    if (tid == 0) { kmin = 0x7fffffff; nan_bound = 0; }
+    const bool nb = cauchy_sort_invert(sa);
+    __syncthreads();
+    if (nb) nan_bound = 1;                                             // (every writer stores the same value; read behind two more barriers)
+    // ---- the terms of this block: prefix of c ascending; shell and g d parked, then their suffixes descending --------------------
+    double p = 0.0;
+    for (int k = lo; k < hi; ++k) {
+        sa.scan[k] = p;
+        CauchySortTerm t{0.0, 0.0, 0.0};
+        if (k < nfree) t = cauchy_sort_term(sa, k);
+        p = __dadd_rn(p, t.c);
+        sa.scan[sl + k] = t.shell; sa.scan[2 * sl + k] = t.gd;
+    }
+    double ws = 0.0, wg = 0.0;
+    for (int k = hi - 1; k >= lo; --k) {
+        ws = __dadd_rn(sa.scan[sl + k], ws); wg = __dadd_rn(sa.scan[2 * sl + k], wg);
+        sa.scan[sl + k] = ws; sa.scan[2 * sl + k] = wg;
+    }
+    totC[tid] = p; totD[0][tid] = ws; totD[1][tid] = wg;
+    __syncthreads();
+    double aD[2], bD[2];
+    const double aC = cauchy_carry_before(totC + 64 * wave, lane);
+    cauchy_carry_behind(&totD[0][64 * wave], T, 63, lane, aD);
+    if (lane == 63) wtC[wave] = __dadd_rn(aC, p);
+    if (lane == 0) { wtD[0][wave] = __dadd_rn(ws, aD[0]); wtD[1][wave] = __dadd_rn(wg, aD[1]); }
+    __syncthreads();
+    const double bC = cauchy_carry_before(wtC, wave);
+    cauchy_carry_behind(&wtD[0][0], NW, NW - 1, wave, bD);
+    const double offC = __dadd_rn(bC, aC), offS = __dadd_rn(aD[0], bD[0]), offG = __dadd_rn(aD[1], bD[1]);
+    totC[tid] = offC; totD[0][tid] = offS; totD[1][tid] = offG;       // (every read of the block totals lies before the barrier above)
+    // ---- the first segment of this block at which the search ends ----------------------------------------------------------------
+    auto segment = [&](int k, double oC, double oS, double oG) {
+        return cauchy_sort_stop(sa, k, nfree, nfix0, __dadd_rn(sa.scan[sl + k], oS), __dadd_rn(oC, sa.scan[k]), __dadd_rn(sa.scan[2 * sl + k], oG));
+    };
+    for (int k = lo; k < hi; ++k) {
+        const CauchySortSeg sg = segment(k, offC, offS, offG);
+        if (sg.q.done || sg.bad) { atomicMin(&kmin, k); break; }
+    }
+    __syncthreads();
+    const int ks = kmin;                                               // (segment nfree always ends the search: nfix0 + nfree = n)
+    const int owner = ks / E;
+    cauchy_sort_finish(sa, segment(ks, totC[owner], totD[0][owner], totD[1][owner]), ks, nfix0, flag_in != 0 || nan_bound != 0);
 }
 
 }  // namespace bh

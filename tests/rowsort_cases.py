@@ -127,23 +127,6 @@ def row_scan(Jt, w, dr, br, grid, fault=None, rows_per_step=256):
     return slabs
 
 
-def _suffix_offsets(tot):
-    """cauchy_sort_scan_kernel: the block totals behind lane l from lane 63 downwards, the wave totals behind wave w likewise; A + B."""
-    nw = SCAN_T // 64
-    t = tot.reshape(nw, 64)
-    a = np.zeros((nw, 64))
-    acc = np.zeros(nw)
-    for u in range(63, -1, -1):
-        a[:, u] = acc
-        acc = t[:, u] + acc
-    bw = np.zeros(nw)
-    accw = 0.0
-    for v in range(nw - 1, -1, -1):
-        bw[v] = accw
-        accw = acc[v] + accw
-    return (a + bw[:, None]).reshape(SCAN_T)
-
-
 RowsResult = namedtuple("RowsResult", "s fix n_hmul err handback kstar phi_p phi_pp terms")
 
 
@@ -163,7 +146,6 @@ def rowsort_search(inst, grid=None, fault=None):
     with np.errstate(invalid="ignore"):
         fix0 = ((x - xlow) <= gc.SQRT_EPS) | ((xupp - x) <= gc.SQRT_EPS)  # active_bounds! (poly:211)
         d_u, d_l = np.minimum(xupp - x, delta), np.maximum(xlow - x, -delta)
-    nfix0, nmm = int(fix0.sum()), n
     Tk, b, rank, order, bad = sc.keys_and_ranks(g, d_l, d_u, fix0, fault if fault in ("tie_order", "b_from_the_wrong_side") else None)
     nfree = order.size
     d = np.where(fix0, 0.0, -g)
@@ -188,38 +170,12 @@ def rowsort_search(inst, grid=None, fault=None):
         for e in range(E - 1, -1, -1):
             wg = gb[:, e] + wg
             Wg[:, e] = wg
-        gsum = (Wg + _suffix_offsets(wg)[:, None]).reshape(pad)
+        gsum = (Wg + sc.block_offsets(wg)[:, None]).reshape(pad)
         phi_pp, Xk = np.zeros(pad), np.zeros(pad)
         m = min(pad, MAXN)
         phi_pp[:m], Xk[:m] = F[:m], X[:m]
-        tprev = np.zeros(pad)
-        tprev[1:nfree + 1] = To
-        tk = np.full(pad, INF)
-        tk[:nfree] = To
-        theta = np.where(np.isfinite(tk), tk - tprev, INF)
-        phi_p = (gsum + Xk) + tprev * phi_pp
-    kstar, q, seg_bad = None, None, False
-    for k in range(nfree + 1):
-        ind = int(order[k]) if k < nfree and math.isfinite(tk[k]) else -1
-        q = sc.decide(float(phi_p[k]), float(phi_pp[k]), float(theta[k]), ind, nfix0 + k, nmm)
-        seg_bad = not (math.isfinite(phi_p[k]) and math.isfinite(phi_pp[k]))
-        if q[0] or seg_bad:
-            kstar = k
-            break
-    terms = dict(T=Tk, b=b, rank=rank, order=order, d=d, phi_p=phi_p[:nfree + 1], phi_pp=phi_pp[:nfree + 1], X=Xk[:nfree + 1],
-                 theta=theta[:nfree + 1], Jt=Jt, w=w, grid=grid)
-    if bad or seg_bad:
-        return RowsResult(None, None, None, None, True, kstar, None, None, terms)
-    done, min_found, err, advance, step, delta_t = q
-    s = np.zeros(n)
-    fix = fix0.copy()
-    fixed_now = order[:kstar]
-    s[fixed_now] = b[fixed_now]
-    fix[fixed_now] = True
-    rest = order[kstar:]
-    with np.errstate(all="ignore"):
-        s[rest] = (0.0 + tprev[kstar] * (-g[rest])) + step * (-g[rest])
-    return RowsResult(s, fix, kstar + 1, err, False, kstar, float(phi_p[kstar]), float(phi_pp[kstar]), terms)
+    head, seg = sc.stop_and_finish(g, b, order, To, fix0, bad, gsum, Xk, phi_pp)
+    return RowsResult(*head, dict(T=Tk, b=b, rank=rank, order=order, d=d, X=Xk[:nfree + 1], Jt=Jt, w=w, grid=grid, **seg))
 
 
 # ------------------------------------------------------------------------------------------------------------ exactness

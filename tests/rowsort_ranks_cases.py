@@ -1,5 +1,5 @@
 """The sorted rows form of the box-constrained Cauchy search on a ROW-SHARDED implicit handle (bh_hess_set_cauchy_rows_ranks;
-csrc/bh_api.hip: cauchy_launch_rows_sorted) restated in float64 NumPy on top of tests/rowsort_cases.py, which is not edited.  Helper
+csrc/bh_api.hip: cauchy_launch_sorted) restated in float64 NumPy on top of tests/rowsort_cases.py, which is not edited.  Helper
 of tests/test_cauchy_rowsort_ranks_gpu.py, proved on the CPU by tests/test_rowsort_ranks_cases_cpu.py.  Not a test.
 
     1. the rows of J are sharded by the rule of bh.row_shard; the rows of C (weight mu) are on rank 0 only, behind its rows of J

@@ -117,6 +117,62 @@ def _fold(parts):
     return out
 
 
+def block_offsets(tot, ascending=False):
+    """cauchy_carry_behind / cauchy_carry_before on the SCAN_T block totals of the scan kernel: descending, the totals behind lane l
+    from lane 63 downwards and the wave totals behind wave w from the last wave downwards, A + B; ascending, those before lane l
+    from lane 0 upwards and before wave w from wave 0 upwards, B + A."""
+    NW = SCAN_T // 64
+    t = tot.reshape(NW, 64)
+    a = np.zeros((NW, 64))
+    acc = np.zeros(NW)
+    for u in (range(64) if ascending else range(63, -1, -1)):
+        a[:, u] = acc
+        acc = (acc + t[:, u]) if ascending else (t[:, u] + acc)
+    bw = np.zeros(NW)
+    accw = 0.0
+    for v in (range(NW) if ascending else range(NW - 1, -1, -1)):
+        bw[v] = accw
+        accw = (accw + acc[v]) if ascending else (acc[v] + accw)
+    return ((bw[:, None] + a) if ascending else (a + bw[:, None])).reshape(SCAN_T)
+
+
+def stop_and_finish(g, b, order, To, fix0, bad, gsum, cross, phi_pp):
+    """What both sorted forms do behind the scanned sums (cauchy_sort_stop, cauchy_sort_finish): theta and phi' of every segment
+    from sum_{r >= k} g d, the cross term (sum_{r < k} c, or X_k) and phi''_k; the first segment at which the search ends; the
+    hand-back (`bad`: the keys' flag), or s and the active set.  Returns the result tuple without its `terms`, and the segment
+    arrays that go into them."""
+    n, nfree, pad = g.shape[0], order.size, phi_pp.shape[0]
+    nfix0, nmm = int(fix0.sum()), n
+    with np.errstate(all="ignore"):
+        tprev = np.zeros(pad)
+        tprev[1:nfree + 1] = To
+        tk = np.full(pad, INF)
+        tk[:nfree] = To
+        theta = np.where(np.isfinite(tk), tk - tprev, INF)
+        phi_p = (gsum + cross) + tprev * phi_pp
+    kstar, q, seg_bad = None, None, False
+    for k in range(nfree + 1):
+        ind = int(order[k]) if k < nfree and math.isfinite(tk[k]) else -1
+        q = decide(float(phi_p[k]), float(phi_pp[k]), float(theta[k]), ind, nfix0 + k, nmm)
+        seg_bad = not (math.isfinite(phi_p[k]) and math.isfinite(phi_pp[k]))
+        if q[0] or seg_bad:
+            kstar = k
+            break
+    seg = dict(phi_p=phi_p[:nfree + 1], phi_pp=phi_pp[:nfree + 1], theta=theta[:nfree + 1])
+    if bad or seg_bad:
+        return (None, None, None, None, True, kstar, None, None), seg
+    done, min_found, err, advance, step, delta_t = q
+    s = np.zeros(n)
+    fix = fix0.copy()
+    fixed_now = order[:kstar]
+    s[fixed_now] = b[fixed_now]
+    fix[fixed_now] = True
+    rest = order[kstar:]
+    with np.errstate(all="ignore"):
+        s[rest] = (0.0 + tprev[kstar] * (-g[rest])) + step * (-g[rest])
+    return (s, fix, kstar + 1, err, False, kstar, float(phi_p[kstar]), float(phi_pp[kstar])), seg
+
+
 SortedResult = namedtuple("SortedResult", "s fix n_hmul err handback kstar phi_p phi_pp terms")
 
 
@@ -134,7 +190,6 @@ def sorted_search(inst, G=None, fault=None):
     with np.errstate(invalid="ignore"):
         fix0 = ((x - xlow) <= gc.SQRT_EPS) | ((xupp - x) <= gc.SQRT_EPS)  # active_bounds! (poly:211)
         d_u, d_l = np.minimum(xupp - x, delta), np.maximum(xlow - x, -delta)
-    nfix0, nmm = int(fix0.sum()), n
     T, b, rank, order, bad = keys_and_ranks(g, d_l, d_u, fix0, fault)
     nfree = order.size
     d = np.where(fix0, 0.0, -g)
@@ -169,55 +224,14 @@ def sorted_search(inst, G=None, fault=None):
             for e in range(E):
                 W[:, e] = ws2
                 ws2 = ws2 + sb[:, e]
-        NW = SCAN_T // 64
-
-        def offsets(tot, ascending):
-            t = tot.reshape(NW, 64)
-            a = np.zeros((NW, 64))
-            acc = np.zeros(NW)
-            for u in (range(64) if ascending else range(63, -1, -1)):
-                a[:, u] = acc
-                acc = (acc + t[:, u]) if ascending else (t[:, u] + acc)
-            bw = np.zeros(NW)
-            accw = 0.0
-            for v in (range(NW) if ascending else range(NW - 1, -1, -1)):
-                bw[v] = accw
-                accw = (accw + acc[v]) if ascending else (acc[v] + accw)
-            return ((bw[:, None] + a) if ascending else (a + bw[:, None])).reshape(SCAN_T)
-        offC = offsets(p, True)
-        offS = offsets(ws if fault != "prefix_for_suffix" else ws2, fault == "prefix_for_suffix")
-        offG = offsets(wg, False)
+        offC = block_offsets(p, True)
+        offS = block_offsets(ws if fault != "prefix_for_suffix" else ws2, fault == "prefix_for_suffix")
+        offG = block_offsets(wg)
         phi_pp = (W + offS[:, None]).reshape(pad)
         gsum = (Wg + offG[:, None]).reshape(pad)
         csum = (offC[:, None] + P).reshape(pad)
-        tprev = np.zeros(pad)
-        tprev[1:nfree + 1] = To
-        tk = np.full(pad, INF)
-        tk[:nfree] = To
-        theta = np.where(np.isfinite(tk), tk - tprev, INF)
-        phi_p = (gsum + csum) + tprev * phi_pp
-    kstar, q = None, None
-    for k in range(nfree + 1):
-        ind = int(order[k]) if k < nfree and math.isfinite(tk[k]) else -1
-        q = decide(float(phi_p[k]), float(phi_pp[k]), float(theta[k]), ind, nfix0 + k, nmm)
-        seg_bad = not (math.isfinite(phi_p[k]) and math.isfinite(phi_pp[k]))
-        if q[0] or seg_bad:
-            kstar = k
-            break
-    terms = dict(T=T, b=b, rank=rank, order=order, U=U, L=L, shell=shell, c=c, gd=gd, phi_p=phi_p[:nfree + 1], phi_pp=phi_pp[:nfree + 1],
-                 theta=theta[:nfree + 1], d=d, G=G)
-    if bad or seg_bad:
-        return SortedResult(None, None, None, None, True, kstar, None, None, terms)
-    done, min_found, err, advance, step, delta_t = q
-    s = np.zeros(n)
-    fix = fix0.copy()
-    fixed_now = order[:kstar]
-    s[fixed_now] = b[fixed_now]
-    fix[fixed_now] = True
-    rest = order[kstar:]
-    with np.errstate(all="ignore"):
-        s[rest] = (0.0 + tprev[kstar] * (-g[rest])) + step * (-g[rest])
-    return SortedResult(s, fix, kstar + 1, err, False, kstar, float(phi_p[kstar]), float(phi_pp[kstar]), terms)
+    head, seg = stop_and_finish(g, b, order, To, fix0, bad, gsum, csum, phi_pp)
+    return SortedResult(*head, dict(T=T, b=b, rank=rank, order=order, U=U, L=L, shell=shell, c=c, gd=gd, d=d, G=G, **seg))
 
 
 # ------------------------------------------------------------------------------------------------------------ exactness
@@ -316,6 +330,20 @@ def edge_cases(n):
                  " the stop lies behind the last finite breakpoint (rank %d, then theta = Inf)" % (len(hits), n - len(hits), len(hits) - 1)))
     # (rank nfree - 1 is reached by gram_cases.k_all_fixed: every variable ends fixed)
     return out
+
+
+def nan_bound_past_the_first_trip(fixed):
+    """n = 1030, 20 rows: a NaN upper bound on variable 1027, which the scan kernel's threads reach on their second trip over the
+    indices (1027 >= CS_SCAN_T).  fixed: the variable sits on its lower bound, so the initial active_bounds! fixes it."""
+    n = 1030
+    rng = np.random.default_rng(3)
+    J = rng.standard_normal((20, n)) / np.sqrt(20.0)
+    g = rng.standard_normal(n)
+    x, xlow, xupp = np.zeros(n), -np.ones(n), np.ones(n)
+    xupp[1027] = np.nan
+    if fixed:
+        x[1027] = xlow[1027]
+    return (J, None, 0.0, None, x, g, xlow, xupp, 10.0)
 
 
 EDGE_SIZES = (1030, 4097)

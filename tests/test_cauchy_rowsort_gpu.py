@@ -270,6 +270,15 @@ def test_launch_count_and_counters(bh):
 
 
 # ------------------------------------------------------------------------------------------------------------ 6. hand-back
+def _outcome(bh, H, inst, mode):
+    """One search as a comparable tuple: (0, bits of s, set, form, n_hmul), or (error code,)."""
+    try:
+        s, fix, info, _, _ = _inst_search(bh, H, inst, mode)
+        return (0, bits(s).tolist(), fix.tolist(), info["form"], info["n_hmul"])
+    except bh.BenlsipHipError as e:
+        return (e.code,)
+
+
 @pytest.mark.parametrize("what", ["nan_g", "nan_bound"])
 def test_non_finite_input_is_handed_back(bh, what):
     """One NaN in g or in a bound of a free variable (n = 6): the call runs on the stepwise path — its return code and bits,
@@ -284,13 +293,8 @@ def test_non_finite_input_is_handed_back(bh, what):
     else:
         xupp[4] = np.nan
     H = bh.AlHessian(J, None, 0.0)
-    got = []
-    for mode in ("stepwise", "sorted"):
-        try:
-            s, fix, info, _, _ = _search(bh, H, np.zeros((0, n)), xlow, xupp, x, g, 10.0, mode)
-            got.append((0, bits(s).tolist(), fix.tolist(), info["form"], info["n_hmul"]))
-        except bh.BenlsipHipError as e:
-            got.append((e.code,))
+    inst = (J, None, 0.0, None, x, g, xlow, xupp, 10.0)
+    got = [_outcome(bh, H, inst, mode) for mode in ("stepwise", "sorted")]
     assert got[0] == got[1], got
     assert H.searches_rows_sorted == 0
     g[2], xupp[4] = 0.25, 1.0
@@ -299,6 +303,28 @@ def test_non_finite_input_is_handed_back(bh, what):
     assert info["form"] == FORM_ROWS_SORTED and H.searches_rows_sorted == 1
     assert np.array_equal(fix, fix0) and info["n_hmul"] == info0["n_hmul"] and relnorm(s, s0) <= 1e-9
     H.close()
+
+
+def test_nan_bound_past_the_scan_kernels_first_trip(bh):
+    """The instance of test_cauchy_sorted_gpu.py (n = 1030, a NaN upper bound on variable 1027: the second trip of the scan kernel's
+    threads over the indices).  (a) the variable free: handed back — the counter unchanged, code and bits the stepwise path's.
+    (b) fixed at the start: the bound is never looked at — a sorted search, set and decisions of the restatement at this device's
+    grid, the step within 1e-9 of it."""
+    inst = rw.sc.nan_bound_past_the_first_trip(False)
+    H = _handle(bh, inst)
+    try:
+        got = [_outcome(bh, H, inst, mode) for mode in ("stepwise", "sorted")]
+        assert got[0] == got[1], [t[:1] + t[3:] for t in got]
+        assert H.searches_rows_sorted == 0
+        inst = rw.sc.nan_bound_past_the_first_trip(True)
+        res = rw.rowsort_search(inst, grid=rw.grid_of(inst[0].shape[0], _n_cu(bh)))
+        assert not res.handback
+        s, fix, info, _, _ = _inst_search(bh, H, inst, "sorted")
+        assert info["form"] == FORM_ROWS_SORTED and H.searches_rows_sorted == 1
+        assert np.array_equal(fix, res.fix) and info["n_hmul"] == res.n_hmul, (info, res.n_hmul)
+        assert relnorm(s, res.s) <= 1e-9, relnorm(s, res.s)
+    finally:
+        H.close()
 
 
 # ------------------------------------------------------------------------------------------------------------ 7. setter and getter, switch off

@@ -212,30 +212,60 @@ def test_no_breakpoint_left_is_the_same_error(bh, n):
 
 
 # ------------------------------------------------------------------------------------------------------------ 8. hand-back
-def test_nan_in_g_is_handed_back(bh):
-    """One NaN in g (n = 6): the call runs on the stepwise path — the same return code, searches_sorted unchanged, and it returns."""
+def _outcome(bh, H, inst, mode):
+    """One search as a comparable tuple: (0, bits of s, set, form, n_hmul), or (error code,)."""
+    try:
+        s, fix, info, _, _ = _inst_search(bh, H, inst, mode)
+        return (0, bits(s).tolist(), fix.tolist(), info["form"], info["n_hmul"])
+    except bh.BenlsipHipError as e:
+        return (e.code,)
+
+
+@pytest.mark.parametrize("what", ["nan_g", "nan_bound"])
+def test_nan_in_g_is_handed_back(bh, what):
+    """One NaN in g or in a bound of a free variable (n = 6): the call runs on the stepwise path — its return code and bits,
+    searches_sorted unchanged — and the handle serves the next, finite call in the sorted form."""
     n = 6
     rng = np.random.default_rng(3)
     J = rng.standard_normal((20, n)) / np.sqrt(20.0)
     g = rng.standard_normal(n)
-    g[2] = np.nan
     x, xlow, xupp = np.zeros(n), -np.ones(n), np.ones(n)
+    if what == "nan_g":
+        g[2] = np.nan
+    else:
+        xupp[4] = np.nan
     H = _gram(bh, J)
-    codes = []
-    for mode in ("stepwise", "sorted"):
-        try:
-            _search(bh, H, np.zeros((0, n)), xlow, xupp, x, g, 10.0, mode)
-            codes.append(0)
-        except bh.BenlsipHipError as e:
-            codes.append(e.code)
-    assert codes[0] == codes[1], codes
+    inst = (J, None, 0.0, None, x, g, xlow, xupp, 10.0)
+    got = [_outcome(bh, H, inst, mode) for mode in ("stepwise", "sorted")]
+    assert got[0] == got[1], got
     assert H.searches_sorted == 0
-    g[2] = 0.25                                                      # the handle serves the next, finite call in the sorted form
+    g[2], xupp[4] = 0.25, 1.0                                        # the handle serves the next, finite call in the sorted form
     s, fix, info, _, _ = _search(bh, H, np.zeros((0, n)), xlow, xupp, x, g, 10.0, "sorted")
     s0, fix0, info0, _, _ = _search(bh, H, np.zeros((0, n)), xlow, xupp, x, g, 10.0, "stepwise")
     assert info["form"] == FORM_SORTED and H.searches_sorted == 1
     assert np.array_equal(fix, fix0) and info["n_hmul"] == info0["n_hmul"] and relnorm(s, s0) <= 1e-9
     H.close()
+
+
+def test_nan_bound_past_the_scan_kernels_first_trip(bh):
+    """(a) variable 1027 free: handed back — the counter unchanged, code and bits the stepwise path's.  (b) fixed at the start: the
+    bound is never looked at — a sorted search, set and decisions of the restatement, the step within 1e-9 of it."""
+    assert 1027 >= sc.SCAN_T
+    inst = sc.nan_bound_past_the_first_trip(False)
+    H = _gram(bh, inst[0])
+    try:
+        got = [_outcome(bh, H, inst, mode) for mode in ("stepwise", "sorted")]
+        assert got[0] == got[1], [t[:1] + t[3:] for t in got]
+        assert H.searches_sorted == 0
+        inst = sc.nan_bound_past_the_first_trip(True)
+        res = sc.sorted_search(inst)
+        assert not res.handback
+        s, fix, info, _, _ = _inst_search(bh, H, inst, "sorted")
+        assert info["form"] == FORM_SORTED and H.searches_sorted == 1
+        assert np.array_equal(fix, res.fix) and info["n_hmul"] == res.n_hmul, (info, res.n_hmul)
+        assert relnorm(s, res.s) <= 1e-9, relnorm(s, res.s)
+    finally:
+        H.close()
 
 
 # ------------------------------------------------------------------------------------------------------------ 9. stale G

@@ -139,6 +139,20 @@ def test_non_finite_input_hands_back():
     assert rw.rowsort_search((J, None, 0.0, None, np.zeros(n), g, -np.ones(n), xupp, 10.0)).handback
 
 
+def test_nan_bound_past_the_first_trip_in_both_restatements():
+    """sorted_cases.nan_bound_past_the_first_trip (n = 1030, xupp[1027] = NaN): free, both restatements hand back; fixed at the
+    start, neither does — 277 decisions, s and the set those of the same instance with a finite bound."""
+    assert sc.sorted_search(sc.nan_bound_past_the_first_trip(False)).handback
+    assert rw.rowsort_search(sc.nan_bound_past_the_first_trip(False)).handback
+    inst = sc.nan_bound_past_the_first_trip(True)
+    xupp = inst[7].copy()
+    xupp[1027] = 1.0
+    for search in (sc.sorted_search, rw.rowsort_search):
+        res, fin = search(inst), search(inst[:7] + (xupp,) + inst[8:])
+        assert not res.handback and res.n_hmul == fin.n_hmul == 277
+        assert np.array_equal(res.s, fin.s) and np.array_equal(res.fix, fin.fix) and res.fix[1027]
+
+
 SERVED_ORACLE_CASES = [c for c in ORACLE_CASES if rw.served(c[1])]
 
 
